@@ -12,7 +12,11 @@ the north star asks for.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps
+and prints the line; --dump-outputs DIR writes the last timed step's localization
+table to DIR as .npy files; --full adds what the headline does not need (the CPU
+baseline, per-kernel times and roofline, the step with every spot in the
+reference's arithmetic), each in runs of its own after the timed steps.
 """
 from __future__ import annotations
 
@@ -47,10 +51,18 @@ def parse():
     ap.add_argument("--method", default="sigmaxy")
     ap.add_argument("--eps", type=float, default=1e-3,
                     help="convergence criterion of the MLE fit (the GUI's default; 1e-4 re-fits 11 %% of the spots: DESIGN.md section 7)")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU-baseline budget (0 = skip)")
-    ap.add_argument("--profile-steps", type=int, default=5, help="extra instrumented steps for per-kernel time")
-    ap.add_argument("--strict-steps", type=int, default=2,
-                    help="extra steps with every spot in the reference's arithmetic (value_strict; 0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure what it does not need: the CPU baseline, the per-kernel times and "
+                         "roofline (extra instrumented passes) and the step with every spot in the reference's arithmetic")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the localization table of the last timed step to DIR/<column>.npy (float32; the integer "
+                         "columns as float64), a fixed seeded sample of its rows where the whole table exceeds 64 MB")
+    ap.add_argument("--cpu-seconds", type=float, default=None, help="CPU-baseline budget (default 15 with --full, else 0 = skip)")
+    ap.add_argument("--profile-steps", type=int, default=None,
+                    help="extra instrumented steps for per-kernel time and the roofline (default 5 with --full, else 0 = skip)")
+    ap.add_argument("--strict-steps", type=int, default=None,
+                    help="extra steps with every spot in the reference's arithmetic (value_strict; default 2 with --full, "
+                         "else 0 = skip)")
     ap.add_argument("--ranges", type=int, default=2, choices=(1, 2),
                     help="frame ranges pmi_localize_mle_dev keeps in flight in the timed steps (2 = the library's default "
                          "schedule: the scan of the second half beside the fit of the first; 1 = one range, as the profiled passes)")
@@ -61,7 +73,15 @@ def parse():
                          "strong = --frames is the whole job, each rank takes frames / N of it")
     ap.add_argument("--serial-gather", action="store_true",
                     help="N > 1: wait for each step's all-gather before the next step computes (no overlap)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    # a plain run does only what the headline needs; --full adds the extra measurements at their budgets, and an explicit
+    # value of one of them applies either way
+    for name, full_default in (("cpu_seconds", 15.0), ("profile_steps", 5), ("strict_steps", 2)):
+        if getattr(args, name) is None:
+            setattr(args, name, full_default if args.full else 0)
+    return args
 
 
 def launch_ranks(args):
@@ -264,13 +284,21 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    last = (args.steps - 1) % nbuf          # the buffer set of the last timed step
     if grouped:
         # the gathered table is what every rank would hand on: check rank order and counts once
-        last = (args.steps - 1) % nbuf if args.steps > 0 else 0
         counts = gathered_n[last].cpu().tolist()
         assert counts[rank] == int(d_ns[last].item()) and all(0 < c <= cap for c in counts), counts
         mine = gathered[last].view(world, _lib.PMI_LOC_COLUMNS, cap)[rank, :, : counts[rank]]
         assert torch.equal(mine, tables[last][:, : counts[rank]]), "gathered table differs from the local one"
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step: the table (with N > 1 every shard's rows, in rank order)
+        if grouped:
+            per_shard = gathered[last].view(world, _lib.PMI_LOC_COLUMNS, cap)
+            rows = torch.cat([per_shard[r, :, : counts[r]] for r in range(world)], dim=1)
+        else:
+            rows = tables[last][:, : int(d_ns[last].item())]
+        dump_outputs(args.dump_outputs, rows.cpu().numpy())
     # where a rank's step went: kernels of the path (compute stream) and, beside them, the all-gather on its side stream
     # (from the moment the step's table was ready to the end of the collective — it includes waiting for the slowest rank)
     compute_ms = float(np.mean([a.elapsed_time(b) for a, b, _ in timeline])) if timeline else float("nan")
@@ -350,27 +378,29 @@ def main():
     result = None
     if rank == 0:
         n_rank0 = int(d_n.item())
-        kernels = {
-            "identify_scan": {"ms": scan_ms, "algorithmic_bytes": movie_bytes,
-                              "GB/s": movie_bytes / (scan_ms * 1e-3) / 1e9 if scan_ms == scan_ms else None},
-            "mle_fit": {"ms": fit_ms, "algorithmic_bytes": FIT_BYTES_PER_SPOT_7 * n_rank0,
-                        "GB/s": FIT_BYTES_PER_SPOT_7 * n_rank0 / (fit_ms * 1e-3) / 1e9 if fit_ms == fit_ms else None,
-                        "spots_per_s": n_rank0 / (fit_ms * 1e-3) if fit_ms == fit_ms else None},
-        }
-        # The roofline object describes the HBM-bound kernel of the path, the frame scan (it moves
-        # 5.24 kB per localization; the fit moves 166 B and is FP32-ALU bound, listed beside it).
-        dom = "identify_scan"
-        ach = kernels[dom]["GB/s"]
-        traffic, traffic_source = pmc_traffic_bytes(F, H, W, box, scan_kernel)
-        roofline = {"bound": "hbm", "kernel": dom, "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": (ach / HBM_PEAK_GBS) if ach else None,
-                    "traffic": traffic, "traffic_source": traffic_source,
-                    "measured_on": f"{args.profile_steps} single-range passes over the whole movie after the timed steps (HIP events "
-                                   "around the kernels on their launch stream, inside the library); the same launches as "
-                                   "`bench.py --ranges 1`, profiles/r06_bench_ranges1_kernel_stats.txt",
-                    "scan_kernel": scan_kernel,
-                    "kernels": kernels}
-        kernels["mle_fit"]["bound"] = "fp32 valu (no MFMA shape); algorithmic bytes are 166 B/spot"
+        roofline = None
+        if args.profile_steps > 0:
+            kernels = {
+                "identify_scan": {"ms": scan_ms, "algorithmic_bytes": movie_bytes,
+                                  "GB/s": movie_bytes / (scan_ms * 1e-3) / 1e9 if scan_ms == scan_ms else None},
+                "mle_fit": {"ms": fit_ms, "algorithmic_bytes": FIT_BYTES_PER_SPOT_7 * n_rank0,
+                            "GB/s": FIT_BYTES_PER_SPOT_7 * n_rank0 / (fit_ms * 1e-3) / 1e9 if fit_ms == fit_ms else None,
+                            "spots_per_s": n_rank0 / (fit_ms * 1e-3) if fit_ms == fit_ms else None},
+            }
+            # The roofline object describes the HBM-bound kernel of the path, the frame scan (it moves
+            # 5.24 kB per localization; the fit moves 166 B and is FP32-ALU bound, listed beside it).
+            dom = "identify_scan"
+            ach = kernels[dom]["GB/s"]
+            traffic, traffic_source = pmc_traffic_bytes(F, H, W, box, scan_kernel)
+            roofline = {"bound": "hbm", "kernel": dom, "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": (ach / HBM_PEAK_GBS) if ach else None,
+                        "traffic": traffic, "traffic_source": traffic_source,
+                        "measured_on": f"{args.profile_steps} single-range passes over the whole movie after the timed steps (HIP events "
+                                       "around the kernels on their launch stream, inside the library); the same launches as "
+                                       "`bench.py --ranges 1`, profiles/r06_bench_ranges1_kernel_stats.txt",
+                        "scan_kernel": scan_kernel,
+                        "kernels": kernels}
+            kernels["mle_fit"]["bound"] = "fp32 valu (no MFMA shape); algorithmic bytes are 166 B/spot"
         cpu = None
         if world == 1 and args.cpu_seconds > 0:
             cpu = cpu_baseline(movie, cam, box, args.min_ng, args.method, args.cpu_seconds, args.eps)
@@ -488,6 +518,28 @@ def cpu_baseline(movie, cam, box, min_ng, method, budget_s, eps=1e-3):
             "sample": f"first {frames} frames of the same movie ({n} spots), identify+get_spots+gaussmle "
                       f"({method}, eps {eps:g}, max_it 100), C/OpenMP restatement of the reference algorithm, "
                       f"{dt:.1f} s"}
+
+
+DUMP_BYTES_MAX = 64_000_000    # --dump-outputs writes at most this many bytes
+DUMP_SEED = 20261016           # the seed of the row sample: the same rows in every run with the same arguments
+
+
+def dump_outputs(out_dir, words):
+    """The localization table as its caller receives it, `words` = PMI_LOC_COLUMNS x n int32 words (rows in (frame, y, x)
+    order), written as DIR/<column>.npy for every column of backend.LOC_COLUMNS: the float32 columns as float32, frame and
+    iterations as float64 (exact).  Beside them n_localizations.npy (the row count n) and row.npy (the index of each written
+    row in the table).  Where all n rows would exceed DUMP_BYTES_MAX, a sample of rows drawn with DUMP_SEED is written."""
+    from picasso_amd.backend import LOC_COLUMNS
+    n = words.shape[1]
+    row_bytes = 8 + sum(4 if dt == np.float32 else 8 for _, dt in LOC_COLUMNS)        # 8: the row index
+    keep = (DUMP_BYTES_MAX - 64 * 1024) // row_bytes                                    # 64 kB: the .npy headers
+    rows = np.arange(n) if n <= keep else np.sort(np.random.default_rng(DUMP_SEED).choice(n, keep, replace=False))
+    out = {"n_localizations": np.array([n], np.float64), "row": rows.astype(np.float64)}
+    for c, (name, dt) in enumerate(LOC_COLUMNS):
+        out[name] = words[c, rows].view(dt).astype(np.float32 if dt == np.float32 else np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 if __name__ == "__main__":

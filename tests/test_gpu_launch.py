@@ -46,7 +46,7 @@ def test_rccl_probe_one_rank():
 
 
 def test_bench_one_gpu_line_and_world_checks():
-    small = ["--steps", "2", "--warmup", "1", "--frames", "400", "--cpu-seconds", "0", "--profile-steps", "1", "--strict-steps", "1"]
+    small = ["--full", "--steps", "2", "--warmup", "1", "--frames", "400", "--cpu-seconds", "0", "--profile-steps", "1", "--strict-steps", "1"]
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + small, cwd=ROOT, env=_env(),
                          capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -62,6 +62,33 @@ def test_bench_one_gpu_line_and_world_checks():
     bad = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + small, cwd=ROOT, env=env,
                          capture_output=True, text=True, timeout=600)
     assert bad.returncode != 0 and "WORLD_SIZE is 2" in bad.stderr
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run measures the headline alone: no CPU baseline, roofline or strict step on its line.  --dump-outputs writes
+    the last timed step's table as float32 / float64 .npy files, at most 64 MB, and two runs with the same arguments
+    write the same bits."""
+    import numpy as np
+    small = ["--steps", "3", "--warmup", "1", "--frames", "400"]
+    lines = []
+    for d in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dump-outputs", str(tmp_path / d)]
+                             + small, cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines.append(json.loads(out.stdout.strip().splitlines()[-1]))
+    line = lines[0]
+    assert line["steps"] == 3 and line["value"] > 1e6 and line["higher_is_better"] is True
+    n = line["config"]["localizations_total"]
+    assert abs(line["value"] - n / (line["ms_per_step"] * 1e-3)) <= 1e-6 * line["value"]
+    assert line["roofline"] is None and line["cpu_baseline"] is None and line["value_strict"] is None
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == sorted(p.name for p in (tmp_path / "b").iterdir())
+    assert {"frame.npy", "x.npy", "y.npy", "photons.npy", "iterations.npy", "n_localizations.npy", "row.npy"} <= set(names)
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) <= 64_000_000
+    assert int(np.load(tmp_path / "a" / "n_localizations.npy")[0]) == n == len(np.load(tmp_path / "a" / "x.npy"))
+    for name in names:
+        a, b = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b, equal_nan=True), name
 
 
 def test_bench_starts_its_own_ranks():

@@ -514,6 +514,32 @@ def test_bench_refuses_tuning_variables():
     assert r.stdout.strip() == ""          # no JSON line
 
 
+def test_bench_dump_outputs_sample(tmp_path):
+    """bench.py --dump-outputs: a table too large for 64 MB is written as a fixed seeded sample of its rows, the same rows in
+    every run; each column in float32 (float64 for the integer columns) with the bits the table holds."""
+    import os
+
+    import bench
+    rng = np.random.default_rng(5)
+    n = 1_000_000
+    words = rng.random((len(backend.LOC_COLUMNS), n), dtype=np.float32).view(np.int32)
+    words[0] = np.sort(rng.integers(0, 10000, n))
+    words[12] = rng.integers(1, 101, n)
+    dumps = []
+    for d in ("a", "b"):
+        out = str(tmp_path / d)
+        bench.dump_outputs(out, words)
+        dumps.append({f[:-4]: np.load(os.path.join(out, f)) for f in os.listdir(out)})
+    a, b = dumps
+    assert set(a) == {name for name, _ in backend.LOC_COLUMNS} | {"row", "n_localizations"} and int(a["n_localizations"][0]) == n
+    assert sum(v.nbytes for v in a.values()) <= 64_000_000 and 0 < len(a["row"]) < n
+    rows = a["row"].astype(np.int64)
+    assert np.all(np.diff(rows) > 0)
+    for c, (name, dt) in enumerate(backend.LOC_COLUMNS):
+        assert a[name].dtype == (np.float32 if dt == np.float32 else np.float64)
+        assert np.array_equal(a[name], words[c, rows].view(dt).astype(a[name].dtype)) and np.array_equal(a[name], b[name]), name
+
+
 def test_lq_chain_scratch_layouts_are_free_of_bank_conflicts():
     """The LDS layout of the strict least-squares Jacobian's chain scratch (csrc/lq_jacobian_w.inc: LqwBox<W> and
     lqw_coff<W>) through the bank model of tools/emul/lds_chain_layout.py (lane groups and bank functions of gfx950's

@@ -8,10 +8,10 @@ rm -rf /tmp/pmc_scan_fused /tmp/pmc_scan_alone /tmp/pmc_g8 /tmp/pmc_g8i /tmp/pmc
 mkdir -p $OUT; export TMPDIR=/tmp
 bash tools/pmc_scan.sh /tmp/pmc_scan_fused 10000 7 fused > $OUT/${TAG}_scan_pmc.txt 2>&1; cp /tmp/pmc_scan_fused/traffic.json $OUT/${TAG}_identify_pmc.json
 cp /tmp/pmc_scan_fused/traffic.json profiles/${TAG}_identify_pmc.json      # bench.py quotes roofline.traffic from this file and checks the kernel
-python3 bench.py > $OUT/${TAG}_bench.json 2> $OUT/bench.err || tail -5 $OUT/bench.err
-(cd /tmp && rocprofv3 --kernel-trace --stats -d /tmp/prof_bench -- python3 $OLDPWD/bench.py --cpu-seconds 0 > /tmp/prof_bench.log 2>&1)
+python3 bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/bench.err || tail -5 $OUT/bench.err
+(cd /tmp && rocprofv3 --kernel-trace --stats -d /tmp/prof_bench -- python3 $OLDPWD/bench.py --full --cpu-seconds 0 > /tmp/prof_bench.log 2>&1)
 python3 tools/rocprof_summary.py /tmp/prof_bench > $OUT/${TAG}_bench_kernel_stats.txt
-(cd /tmp && rocprofv3 --kernel-trace --stats -d /tmp/prof_bench1 -- python3 $OLDPWD/bench.py --cpu-seconds 0 --ranges 1 > /tmp/prof_bench1.log 2>&1)
+(cd /tmp && rocprofv3 --kernel-trace --stats -d /tmp/prof_bench1 -- python3 $OLDPWD/bench.py --full --cpu-seconds 0 --ranges 1 > /tmp/prof_bench1.log 2>&1)
 python3 tools/rocprof_summary.py /tmp/prof_bench1 > $OUT/${TAG}_bench_ranges1_kernel_stats.txt
 bash tools/pmc_scan.sh /tmp/pmc_scan_alone 10000 7 identify > $OUT/${TAG}_scan_alone_pmc.txt 2>&1; cp /tmp/pmc_scan_alone/traffic.json $OUT/${TAG}_identify_alone_pmc.json
 bash tools/pmc_fit.sh /tmp/pmc_g8 "g8_iterate" python3 tools/ab_defer.py 10000 7 1 1 > $OUT/${TAG}_g8_iterate_pmc.txt 2>&1
