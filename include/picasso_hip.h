@@ -43,6 +43,11 @@
  *   pmi_localize_mle_dev    picasso/localize.py:1682-1815 localize with
  *                      fitting_method="gaussmle" (identify -> get_spots -> fit
  *                      -> table) as one asynchronous device pipeline
+ *   pmi_aim_*          picasso/aim.py:517-659 intersection_max, :662-773
+ *                      intersection_max_z (-> :89-126 _count_intersections,
+ *                      :206-250 _run_intersections_multithread, :275-320
+ *                      _point_intersect_2d, :349-397 _point_intersect_3d): the
+ *                      roi_cc counts of AIM undrift (:776-950 aim)
  */
 #ifndef PICASSO_HIP_H
 #define PICASSO_HIP_H
@@ -435,6 +440,40 @@ int pmi_fft_prewarm(int64_t Y, int64_t X);
 int pmi_peak_fit(const double *rois, int64_t n, int box, double *popt, int32_t *status);
 int pmi_rcc_shifts(const double *segments, int64_t n_seg, int64_t Y, int64_t X, int64_t roi, int box,
                    const int32_t *pairs, int64_t n_pairs, double *shift_yx, int32_t *fit_status);
+
+/* ---- AIM undrift: intersection counts (picasso/aim.py:517-773, csrc/aim.hip) ---------------------- *
+ * Key arithmetic of a round (the reference's column dtypes, see aim.hip):
+ *   PMI_AIM_XY_F32  x / y round 1: float32 x, y; rel added in float32
+ *   PMI_AIM_XY_F64  x / y round 2: float64 x, y
+ *   PMI_AIM_Z_F32   z round 1: float64 x, y; float32 z (already divided by the pixel size); rel added to z in float32
+ *   PMI_AIM_Z_F64   z round 2: float64 x, y, z
+ * shifts: n_shifts int32 (x / y modes: the reference's shifts_xy, row-major box x box) or float64 (z modes: shifts_z).
+ * pmi_aim_partition_dev  d_frame: n int64 frames numbered from 1 (aim.py:852); rows of segment s (frames in
+ *                        (s * seg_len, min((s + 1) * seg_len, n_frames)]) go to d_rows[seg_offsets[s] .. seg_offsets[s+1]),
+ *                        in no particular order; rows outside [1, n_frames] to none.  seg_offsets: host, ceil(n_frames /
+ *                        seg_len) + 1 entries.  Synchronises `stream`.
+ * pmi_aim_table_create_dev  counts the reference keys of rows d_rows[0 .. n_ref) (NULL: rows 0 .. n_ref-1) of the device
+ *                        columns once per round; returns an opaque table that owns its device memory.  Synchronises.
+ * pmi_aim_count_dev      roi_cc of the target rows d_rows[0 .. n_rows) shifted by rel: d_out[0 .. n_shifts) = the counts,
+ *                        d_out[n_shifts] = status (0 ok; 1 the target hash overflowed).  Asynchronous on `stream`; a table
+ *                        serves one stream at a time.
+ * pmi_aim_roi_cc         the same for host columns (one table, one count), -> int64 roi_cc[n_shifts].
+ * pmi_aim_set_dense_limit  spans of more target-counter entries than this (default 2^28) take the sorted form.         */
+enum pmi_aim_mode { PMI_AIM_XY_F32 = 0, PMI_AIM_XY_F64 = 1, PMI_AIM_Z_F32 = 2, PMI_AIM_Z_F64 = 3 };
+int pmi_aim_set_dense_limit(int64_t entries);
+int pmi_aim_partition_dev(const int64_t *d_frame, int64_t n, int64_t seg_len, int64_t n_frames, int32_t *d_rows,
+                          int64_t *seg_offsets, void *stream);
+int pmi_aim_table_create_dev(int mode, const void *d_x, const void *d_y, const void *d_z, const int32_t *d_rows,
+                             int64_t n_ref, double intersect_d, double width_units, double height_units,
+                             const void *shifts, int n_shifts, void **table, void *stream);
+int pmi_aim_table_info(void *table, int *dense, int64_t *entries);   /* dense: 1 dense form, 0 sorted; entries of it */
+int pmi_aim_count_dev(void *table, const void *d_x, const void *d_y, const void *d_z, const int32_t *d_rows,
+                      int64_t n_rows, double rel_x, double rel_y, double rel_z, int32_t *d_out, void *stream);
+int pmi_aim_table_destroy(void *table);
+int pmi_aim_roi_cc(int mode, const void *ref_x, const void *ref_y, const void *ref_z, int64_t n_ref, const void *x,
+                   const void *y, const void *z, int64_t n, double rel_x, double rel_y, double rel_z,
+                   double intersect_d, double width_units, double height_units, const void *shifts, int n_shifts,
+                   int64_t *roi_cc);
 
 /* ---- timing hooks for bench.py (HIP events on the given stream) ------- */
 int pmi_event_create(void **event);

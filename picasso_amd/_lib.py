@@ -105,6 +105,13 @@ SYMBOLS = {
     "pmi_comm_destroy": (_i32, [_p]),
     "pmi_allgather_locs": (_i32, [_p, _p, _i32, _i64, _p, _p, _p, _p]),
     "pmi_compact_gathered_dev": (_i32, [_p, _p, _i32, _i32, _i64, _p, _i64, _p, _p]),
+    "pmi_aim_set_dense_limit": (_i32, [_i64]),
+    "pmi_aim_partition_dev": (_i32, [_p, _i64, _i64, _i64, _p, _p, _p]),
+    "pmi_aim_table_create_dev": (_i32, [_i32, _p, _p, _p, _p, _i64, _f64, _f64, _f64, _p, _i32, _p, _p]),
+    "pmi_aim_table_info": (_i32, [_p, _p, _p]),
+    "pmi_aim_count_dev": (_i32, [_p, _p, _p, _p, _p, _i64, _f64, _f64, _f64, _p, _p]),
+    "pmi_aim_table_destroy": (_i32, [_p]),
+    "pmi_aim_roi_cc": (_i32, [_i32, _p, _p, _p, _i64, _p, _p, _p, _i64, _f64, _f64, _f64, _f64, _f64, _f64, _p, _i32, _p]),
     "pmi_event_create": (_i32, [_p]),
     "pmi_event_record": (_i32, [_p, _p]),
     "pmi_event_elapsed_ms": (_i32, [_p, _p, _p]),

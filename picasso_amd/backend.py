@@ -594,3 +594,103 @@ def localize_lq_device(d_movie_ptr, dtype, shape, box, min_ng, camera, roi=None,
                                    em, table, cap_, dn, stream_)
         _lib.check(rc, "pmi_localize_lq_dev")
     return _localize_device(call, LQ_COLUMNS, d_movie_ptr, dtype, shape, roi, frame_bounds, cap, stream, f_lo, f_hi, work)
+
+
+# ---- AIM undrift: intersection counts (csrc/aim.hip, picasso/aim.py:517-773) ----
+AIM_XY_F32, AIM_XY_F64, AIM_Z_F32, AIM_Z_F64 = 0, 1, 2, 3
+
+
+def aim_partition(d_frame, seg_len: int, n_frames: int):
+    """Rows of a resident int64 frame column (numbered from 1) grouped by AIM segment on the device ->
+    (d_rows int32 tensor, host offsets of ceil(n_frames / seg_len) + 1 entries)."""
+    import torch
+    n = int(d_frame.numel())
+    n_seg = -(-int(n_frames) // int(seg_len)) if n_frames > 0 else 0
+    rows = torch.empty(max(n, 1), dtype=torch.int32, device=d_frame.device)
+    offsets = np.zeros(n_seg + 1, np.int64)
+    stream = torch.cuda.current_stream(d_frame.device).cuda_stream
+    with _lib.lock():
+        _lib.check(_lib.load().pmi_aim_partition_dev(ctypes.c_void_p(d_frame.data_ptr()), n, int(seg_len), int(n_frames),
+                                                     ctypes.c_void_p(rows.data_ptr()), _lib.ptr(offsets),
+                                                     ctypes.c_void_p(stream)), "pmi_aim_partition_dev")
+    return rows, offsets
+
+
+def _dptr(t):
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+class AimTable:
+    """The reference keys of one AIM round, counted once on the device (pmi_aim_table_create_dev); `count` gives the
+    roi_cc of one segment of target rows of the same resident columns."""
+
+    def __init__(self, mode, x, y, z, ref_rows, n_ref, intersect_d, width_units, height_units, shifts):
+        import torch
+        self.mode, self.x, self.y, self.z = int(mode), x, y, z
+        self.shifts = np.ascontiguousarray(shifts, np.int32 if mode in (AIM_XY_F32, AIM_XY_F64) else np.float64)
+        self.n_shifts = int(self.shifts.size)
+        self.device = x.device
+        self.stream = torch.cuda.current_stream(self.device).cuda_stream
+        self.out = torch.zeros(self.n_shifts + 1, dtype=torch.int32, device=self.device)
+        self._h = ctypes.c_void_p()
+        with _lib.lock():
+            _lib.check(_lib.load().pmi_aim_table_create_dev(
+                self.mode, _dptr(x), _dptr(y), _dptr(z), _dptr(ref_rows), int(n_ref), float(intersect_d),
+                float(width_units), float(height_units), _lib.ptr(self.shifts), self.n_shifts, ctypes.byref(self._h),
+                ctypes.c_void_p(self.stream)), "pmi_aim_table_create_dev")
+
+    def info(self):
+        dense, entries = ctypes.c_int(0), ctypes.c_int64(0)
+        _lib.check(_lib.load().pmi_aim_table_info(self._h, ctypes.byref(dense), ctypes.byref(entries)), "pmi_aim_table_info")
+        return ("dense" if dense.value else "sorted"), int(entries.value)
+
+    def count(self, rows, rel_x=0.0, rel_y=0.0, rel_z=0.0) -> np.ndarray:
+        """int64 roi_cc of the target rows `rows` (an int32 device tensor) shifted by rel; one D2H of n_shifts + 1 ints."""
+        with _lib.lock():
+            _lib.check(_lib.load().pmi_aim_count_dev(
+                self._h, _dptr(self.x), _dptr(self.y), _dptr(self.z), _dptr(rows), int(rows.numel()), float(rel_x),
+                float(rel_y), float(rel_z), _dptr(self.out), ctypes.c_void_p(self.stream)), "pmi_aim_count_dev")
+            h = self.out.cpu().numpy()
+        if h[-1]:
+            raise _lib.HipBackendError(f"pmi_aim_count_dev: status {int(h[-1])} (target hash overflow)")
+        return h[:-1].astype(np.int64)
+
+    def close(self):
+        if self._h:
+            _lib.load().pmi_aim_table_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def aim_set_dense_limit(entries: int) -> None:
+    """Spans of more target-counter entries than this take the sorted table form (default 2**28)."""
+    _lib.check(_lib.load().pmi_aim_set_dense_limit(int(entries)), "pmi_aim_set_dense_limit")
+
+
+def aim_roi_cc_arrays(mode, ref, target, rel, intersect_d, width_units, height_units, shifts) -> np.ndarray:
+    """roi_cc of one segment from host columns (pmi_aim_roi_cc): ref / target = (x, y[, z]) in the dtypes of `mode`."""
+    _lib.require_gpu()
+    xy_t = np.float32 if mode == AIM_XY_F32 else np.float64
+    z_t = np.float32 if mode == AIM_Z_F32 else np.float64
+    zmode = mode in (AIM_Z_F32, AIM_Z_F64)
+
+    def cols(c):
+        out = [np.ascontiguousarray(c[0], xy_t), np.ascontiguousarray(c[1], xy_t)]
+        out.append(np.ascontiguousarray(c[2], z_t) if zmode else None)
+        return out
+    r, t = cols(ref), cols(target)
+    sh = np.ascontiguousarray(shifts, np.float64 if zmode else np.int32)
+    out = np.zeros(sh.size, np.int64)
+    rel = tuple(rel) + (0.0,) * (3 - len(rel))
+    with _lib.lock():
+        _lib.check(_lib.load().pmi_aim_roi_cc(int(mode), _lib.ptr(r[0]), _lib.ptr(r[1]), _lib.ptr(r[2]), len(r[0]),
+                                              _lib.ptr(t[0]), _lib.ptr(t[1]), _lib.ptr(t[2]), len(t[0]),
+                                              float(rel[0]), float(rel[1]), float(rel[2]), float(intersect_d),
+                                              float(width_units), float(height_units), _lib.ptr(sh), int(sh.size),
+                                              _lib.ptr(out)), "pmi_aim_roi_cc")
+    return out

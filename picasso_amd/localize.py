@@ -795,7 +795,7 @@ def _reference_module(given, name: str):
 
 def install(picasso_localize=None, picasso_gaussmle=None, picasso_gausslq=None, picasso_zfit=None,
             picasso_render=None, picasso_imageprocess=None, picasso_postprocess=None, *, fused: bool = False,
-            devices=None) -> None:
+            devices=None, picasso_aim=None) -> None:
     """Rebind the reference package's hot-path functions to this backend, so that
     picasso.__main__ and the GUI run on the GPU unchanged.  Modules not given are taken
     from the installed ``picasso`` package; the rows next to the path (z fit, render, RCC undrift) are rebound
@@ -804,7 +804,9 @@ def install(picasso_localize=None, picasso_gaussmle=None, picasso_gausslq=None, 
     ``fused=True`` also rebinds ``picasso.localize.localize`` (what `picasso localize` calls, picasso/__main__.py:1086)
     to this package's: same arguments, table and metadata, but the movie crosses PCIe once (`localize_streamed`) instead
     of once for `identify` and once for `get_spots`.  ``devices`` (see `set_devices`) then spreads the frame chunks over
-    several GPUs of the process."""
+    several GPUs of the process.  ``picasso_aim`` (default: ``picasso.aim`` when it imports) gets this package's AIM
+    undrift (``aim``, ``intersection_max``, ``intersection_max_z``), which the Localize GUI, Render and
+    `picasso aim` call."""
     if picasso_localize is None:
         import picasso.localize as picasso_localize       # the installed reference
     if picasso_gaussmle is None:
@@ -860,3 +862,8 @@ def install(picasso_localize=None, picasso_gaussmle=None, picasso_gausslq=None, 
         from . import postprocess as amd_pp
         for name in ("segment", "undrift"):
             setattr(picasso_postprocess, name, getattr(amd_pp, name))
+    picasso_aim = _reference_module(picasso_aim, "aim")
+    if picasso_aim is not None:
+        from . import aim as amd_aim
+        for name in ("aim", "intersection_max", "intersection_max_z"):
+            setattr(picasso_aim, name, getattr(amd_aim, name))
