@@ -71,10 +71,6 @@ struct FitParams {
     float *spots_out;      // g8_init from a movie: the photon values of every spot of the batch are kept here (batch-relative)
     const void *movie;
     const int32_t *frame, *y, *x;
-    // pixel hand-off (uint16 movies): where the scan's exact stage left the box rows of spot i — pix[slot[i]], box rows of
-    // box / 2 + 1 packed uint16 pairs — or slot[i] < 0 / slot == nullptr: read the movie
-    const uint32_t *pix;
-    const int32_t *slot;
     int dtype;
     int64_t Y, X;
     float baseline, sensitivity, gain;

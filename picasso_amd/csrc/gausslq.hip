@@ -704,13 +704,8 @@ static int lq_mode_now()
     }
     return g_lq_mode;
 }
-// statistics of the calling thread's last fit: a device buffer of its own ([0] spots fitted again, [1..7] why), read when asked for
-static thread_local const unsigned *g_lq_stats[2] = {nullptr, nullptr};          // [1]: the second frame range of a fused call
-static thread_local unsigned g_lq_stats_generation = 0;
-static thread_local hipEvent_t g_lq_stats_done[2] = {nullptr, nullptr};       // recorded after the statistics kernel of the fit (the caller's stream may be gone when they are read); the events belong to the device's side lane (runtime.hip), not to this thread
-static thread_local int g_lq_stats_device = 0;
-static thread_local int g_lq_stats_bank = 0;      // and the scratch bank they were taken from
-static thread_local bool g_lq_stats_second = false;                               // the fit being queued is that second range
+// statistics of the calling thread's last fit ([0] spots fitted again, [1..8] why), read when asked for
+static thread_local LastFitStats g_lq_stats;
 static thread_local int g_lq_rounds[2] = {0, 0};
 
 __global__ void lq_stats_add_kernel(const unsigned *__restrict__ tie_n, unsigned *__restrict__ stats, int refitted)
@@ -732,9 +727,10 @@ static void launch_finish(int shape, dim3 grid, size_t lds, hipStream_t s, const
 // still running — on photon data every fit is done by then —, one launch of lq_finish_kernel for whatever is left, then
 // the second pass of the mode (refit: the spots with a decision near its threshold; strict: those with a float32
 // rounding that hangs on the last bit of an exp) as start values + one lq_finish_kernel over the tie list.  Every
-// count lives on the device: nothing here waits for the stream.
+// count lives on the device: nothing here waits for the stream.  range: which frame range of a fused call this fit is (1: the
+// second; its statistics add to the first's), 0 otherwise.
 template <bool FROM_MOVIE_IN>
-static int launch(Params p, hipStream_t s)
+static int launch(Params p, int range, hipStream_t s)
 {
     constexpr bool FROM_MOVIE = false;             // the rounds always read (N, box, box) float32 spots (lq_cut_kernel)
     const int cus = device_cu_count();
@@ -820,30 +816,8 @@ static int launch(Params p, hipStream_t s)
         }
         PMI_HIP(hipGetLastError());
     }
-    g_lq_stats_device = current_device();
-    g_lq_stats_bank = scratch_user_bank();
-    SideLane *lane = nullptr;
-    { const int rc_lane = side_lane(1, &lane); if (rc_lane != PMI_OK) return rc_lane; }
-    hipEvent_t done = g_lq_stats_done[g_lq_stats_second ? 1 : 0] = lane->stats_done[g_lq_stats_second ? 1 : 0];
-    PMI_HIP(hipEventRecord(done, s));
-    g_lq_stats[g_lq_stats_second ? 1 : 0] = stats;
-    if (!g_lq_stats_second) g_lq_stats[1] = nullptr;
-    g_lq_stats_generation = scratch_generation_of(g_lq_stats_device, g_lq_stats_bank, SCR_LQ_STATS);
+    if ((rc = g_lq_stats.record(1, range, stats, s)) != PMI_OK) return rc;
     g_lq_rounds[0] = rounds; g_lq_rounds[1] = no_strict ? 0 : 1;
-    return PMI_OK;
-}
-
-static int read_lq_stats(unsigned (&h)[16])
-{
-    for (unsigned &v : h) v = 0;
-    if (!g_lq_stats[0] || g_lq_stats_generation != scratch_generation_of(g_lq_stats_device, g_lq_stats_bank, SCR_LQ_STATS)) return PMI_OK;      // no fit yet, or its buffers are gone
-    for (int k = 0; k < 2; k++) {
-        if (!g_lq_stats[k]) continue;
-        unsigned part[16];
-        PMI_HIP(hipEventSynchronize(g_lq_stats_done[k]));
-        PMI_HIP(hipMemcpy(part, g_lq_stats[k], 64, hipMemcpyDeviceToHost));
-        for (int i = 0; i < 16; i++) h[i] += part[i];
-    }
     return PMI_OK;
 }
 
@@ -852,6 +826,25 @@ static int check_box(int box)
     // scipy refuses m < n ("func input vector length N=6 must not exceed func output vector length M")
     if (box < 3 || box > PMI_MAX_BOX || (box & 1) == 0) { set_error("gausslq needs an odd box in [3, %d], got %d", PMI_MAX_BOX, box); return PMI_ERR_ARG; }
     return PMI_OK;
+}
+
+// the fit of identifications in a movie: pmi_gausslq_movie_dev, and each frame range of pmi_localize_lq_dev (range: see launch)
+static int fit_movie(const void *d_movie, int dtype, int64_t Y, int64_t X, const int32_t *d_frame, const int32_t *d_y,
+                     const int32_t *d_x, int64_t N, const int64_t *d_n, int box, double baseline, double sensitivity, double gain,
+                     float *d_thetas, int32_t *d_info, int32_t *d_nfev, int range, hipStream_t s)
+{
+    int rc = check_box(box);
+    if (rc != PMI_OK) return rc;
+    if (dtype < 0 || dtype > PMI_F32) { set_error("unknown dtype code %d", dtype); return PMI_ERR_ARG; }
+    if (N <= 0) return PMI_OK;
+    Params p = {};
+    p.movie = d_movie; p.dtype = dtype; p.Y = Y; p.X = X; p.frame = d_frame; p.y = d_y; p.x = d_x;
+    p.baseline = (float)baseline; p.sensitivity = (float)sensitivity; p.gain = (float)gain; p.gdiv = make_const_div((float)gain);
+    p.N = N; p.d_n = d_n; p.box = box; p.thetas = d_thetas; p.info = d_info; p.nfev = d_nfev;
+    ScopedKernelTimer tm(s, &g_last_times.fit_ms);
+    rc = launch<true>(p, range, s);
+    tm.stop();
+    return rc;
 }
 
 // ---- locs_from_fits (gausslq.py:404-484, :547-589) -------------------------
@@ -905,7 +898,7 @@ __global__ void locs_from_fits_lq_kernel(const int32_t *__restrict__ frame, cons
 int identify_impl(const void *d_movie, int dtype, int64_t F, int64_t Y, int64_t X, int box, double min_ng,
                   const int64_t *roi4, int64_t f_lo, int64_t f_hi, int64_t label_offset,
                   int32_t *d_frame, int32_t *d_y, int32_t *d_x, float *d_ng, int64_t cap, int64_t *d_out_n,
-                  hipStream_t s);
+                  bool defer_exact, hipStream_t s);
 
 }  // namespace pmi
 
@@ -928,7 +921,7 @@ int pmi_gausslq_get_mode(int *mode)
 int pmi_gausslq_last_refit_count(int64_t *n_refit)
 {
     unsigned h[16];
-    const int rc = pmi::lq::read_lq_stats(h);
+    const int rc = pmi::lq::g_lq_stats.read(h);
     if (rc != PMI_OK) return rc;
     if (n_refit) *n_refit = h[0];
     return PMI_OK;
@@ -937,7 +930,7 @@ int pmi_gausslq_last_refit_count(int64_t *n_refit)
 int pmi_gausslq_last_tie_reasons(int64_t *counts, int n)
 {
     unsigned h[16];
-    const int rc = pmi::lq::read_lq_stats(h);
+    const int rc = pmi::lq::g_lq_stats.read(h);
     if (rc != PMI_OK) return rc;
     for (int i = 0; counts && i < n; i++) counts[i] = i < 8 ? h[1 + i] : (i < 10 ? pmi::lq::g_lq_rounds[i - 8] : 0);
     return PMI_OK;
@@ -953,7 +946,7 @@ int pmi_gausslq_dev(const float *d_spots, int64_t N, const int64_t *d_n, int box
     lq::Params p = {};
     p.spots = d_spots; p.N = N; p.d_n = d_n; p.box = box; p.thetas = d_thetas; p.info = d_info; p.nfev = d_nfev;
     ScopedKernelTimer tm((hipStream_t)stream, &g_last_times.fit_ms);
-    rc = lq::launch<false>(p, (hipStream_t)stream);
+    rc = lq::launch<false>(p, 0, (hipStream_t)stream);
     tm.stop();
     return rc;
 }
@@ -964,19 +957,8 @@ int pmi_gausslq_movie_dev(const void *d_movie, int dtype, int64_t F, int64_t Y, 
                           float *d_thetas, int32_t *d_info, int32_t *d_nfev, void *stream)
 {
     (void)F;
-    using namespace pmi;
-    int rc = lq::check_box(box);
-    if (rc != PMI_OK) return rc;
-    if (dtype < 0 || dtype > PMI_F32) { set_error("unknown dtype code %d", dtype); return PMI_ERR_ARG; }
-    if (N <= 0) return PMI_OK;
-    lq::Params p = {};
-    p.movie = d_movie; p.dtype = dtype; p.Y = Y; p.X = X; p.frame = d_frame; p.y = d_y; p.x = d_x;
-    p.baseline = (float)baseline; p.sensitivity = (float)sensitivity; p.gain = (float)gain; p.gdiv = make_const_div((float)gain);
-    p.N = N; p.d_n = d_n; p.box = box; p.thetas = d_thetas; p.info = d_info; p.nfev = d_nfev;
-    ScopedKernelTimer tm((hipStream_t)stream, &g_last_times.fit_ms);
-    rc = lq::launch<true>(p, (hipStream_t)stream);
-    tm.stop();
-    return rc;
+    return pmi::lq::fit_movie(d_movie, dtype, Y, X, d_frame, d_y, d_x, N, d_n, box, baseline, sensitivity, gain, d_thetas, d_info,
+                              d_nfev, 0, (hipStream_t)stream);
 }
 
 int pmi_gausslq(const float *spots, int64_t N, int box, float *thetas, int32_t *info, int32_t *nfev)
@@ -1017,28 +999,8 @@ int pmi_locs_from_fits_lq_dev(const int32_t *d_frame, const int32_t *d_y, const 
     return PMI_OK;
 }
 
-namespace pmi {
-namespace lq {
-// rows: [0] rows of A to fit, [1] rows of B to fit, [2] rows of A for the table, [3] rows of B for the table, [4] row offset of B
-__global__ void lq_rows_a_kernel(const int64_t *__restrict__ n_a, int64_t cap, int64_t *__restrict__ rows) { rows[0] = *n_a > cap ? 0 : *n_a; }
-__global__ void lq_rows_b_kernel(const int64_t *__restrict__ n_a, const int64_t *__restrict__ n_b, int64_t cap, int64_t *__restrict__ rows,
-                                 int64_t *__restrict__ d_out_n)
-{
-    const int64_t a = *n_a, b = *n_b, total = a + b;
-    const bool fits = total <= cap;
-    rows[1] = fits ? b : 0;
-    rows[2] = fits ? a : 0;
-    rows[3] = fits ? b : 0;
-    rows[4] = a;
-    *d_out_n = total;
-}
-}  // namespace lq
-}  // namespace pmi
-
-// identify -> fused cut + least-squares fit -> table.  Nothing in here waits for the stream (the fit's loops live on the
-// device, lq::launch), so a large frame range is cut in two like pmi_localize_mle_dev's: the scan of the second half — bound
-// by the memory side — runs on a side stream of the library beside the fit of the first, which is bound by instruction issue;
-// the table is written once both counts are known, A's rows, then B's.
+// identify -> fused cut + least-squares fit -> table, in one or two frame ranges (fused_ranges, runtime.hip).  Nothing in here
+// waits for the stream (the fit's loops live on the device, lq::launch).
 int pmi_localize_lq_dev(const void *d_movie, int dtype, int64_t F, int64_t Y, int64_t X, int box, double min_ng,
                         const int64_t *roi4, int64_t f_lo, int64_t f_hi, double baseline, double sensitivity,
                         double gain, int em, void *d_table, int64_t cap, int64_t *d_out_n, void *stream)
@@ -1047,85 +1009,38 @@ int pmi_localize_lq_dev(const void *d_movie, int dtype, int64_t F, int64_t Y, in
     if (cap <= 0) { set_error("capacity must be positive"); return PMI_ERR_ARG; }
     int rc = lq::check_box(box);
     if (rc != PMI_OK) return rc;
-    hipStream_t s = (hipStream_t)stream;
     struct Ids { int32_t *f, *y, *x; float *ng, *th; };
-    auto carve = [&](void *ptr) {
+    auto carve = [=](void *ptr) {
         Ids d;
         d.f = (int32_t *)ptr; d.y = d.f + cap; d.x = d.y + cap;
         d.ng = (float *)(d.x + cap);
         d.th = d.ng + cap;
         return d;
     };
-    const size_t ids_bytes = (size_t)cap * (16 + 6 * 4);
     lq::LqCols cols;
     for (int c = 0; c < PMI_LQ_COLUMNS; c++) cols.c[c] = (char *)d_table + (size_t)c * cap * 4;
-    const unsigned tblocks = (unsigned)((cap + 255) / 256);
-    void *ptr = nullptr, *cptr = nullptr;
-    if ((rc = scratch(SCR_ROWS, 8 * sizeof(int64_t), &cptr)) != PMI_OK) return rc;
-    int64_t *d_na = (int64_t *)cptr, *d_nb = d_na + 1, *rows = d_na + 2;
-    const int64_t lo = f_lo < 0 ? 0 : f_lo, hi = f_hi > F - 1 ? F - 1 : f_hi, nf = hi - lo + 1;
-    const bool two = g_localize_ranges == 2 && !g_kernel_timing && nf >= 16 && (double)nf * (double)Y * (double)X >= 2.5e8;
-    if (!two) {
-        if ((rc = scratch(SCR_IDS, ids_bytes, &ptr)) != PMI_OK) return rc;
-        const Ids d = carve(ptr);
-        rc = identify_impl(d_movie, dtype, F, Y, X, box, min_ng, roi4, f_lo, f_hi, 0, d.f, d.y, d.x, d.ng, cap, d_out_n, s);
-        if (rc != PMI_OK) return rc;
-        hipLaunchKernelGGL(lq::lq_rows_a_kernel, dim3(1), dim3(1), 0, s, (const int64_t *)d_out_n, cap, rows);
-        rc = pmi_gausslq_movie_dev(d_movie, dtype, F, Y, X, d.f, d.y, d.x, cap, rows + 0, box, baseline, sensitivity,
-                                   gain, d.th, nullptr, nullptr, stream);
-        if (rc != PMI_OK) return rc;
-        hipLaunchKernelGGL(lq::locs_from_fits_lq_kernel, dim3(tblocks), dim3(256), 0, s, d.f, d.y, d.x, d.ng, d.th, cap,
-                           (const int64_t *)(rows + 0), em, cols, (const int64_t *)nullptr);
+    FusedRanges fr;
+    fr.ids_bytes = (size_t)cap * (16 + 6 * 4);
+    fr.capc = cap;
+    fr.cap = cap;
+    fr.rejects = false;
+    fr.scan = [&](void *ids, int64_t lo, int64_t hi, int64_t *d_cnt, hipStream_t st) {
+        const Ids d = carve(ids);
+        return identify_impl(d_movie, dtype, F, Y, X, box, min_ng, roi4, lo, hi, 0, d.f, d.y, d.x, d.ng, cap, d_cnt, false, st);
+    };
+    fr.fit = [&](void *ids, const int64_t *d_rows, int range, hipStream_t st) {
+        const Ids d = carve(ids);
+        return lq::fit_movie(d_movie, dtype, Y, X, d.f, d.y, d.x, cap, d_rows, box, baseline, sensitivity, gain, d.th, nullptr,
+                             nullptr, range, st);
+    };
+    fr.table = [&](void *ids, const int64_t *d_rows, const int64_t *d_row0, hipStream_t st) {
+        const Ids d = carve(ids);
+        hipLaunchKernelGGL(lq::locs_from_fits_lq_kernel, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, st, d.f, d.y, d.x, d.ng,
+                           d.th, cap, d_rows, em, cols, d_row0);
         PMI_HIP(hipGetLastError());
         return PMI_OK;
-    }
-    SideLane *side_p = nullptr;
-    if ((rc = side_lane(1, &side_p)) != PMI_OK) return rc;
-    SideLane &side = *side_p;
-    const int64_t mid = lo + nf / 2 - 1;                      // A = [lo, mid], B = [mid + 1, hi]
-    if ((rc = scratch(SCR_IDS, ids_bytes, &ptr)) != PMI_OK) return rc;
-    const Ids a = carve(ptr);
-    PMI_HIP(hipEventRecord(side.ev_start, s));
-    PMI_HIP(hipStreamWaitEvent(side.s2, side.ev_start, 0));
-    struct Join {       // whatever happens, the caller's stream is ordered after the side stream before this call returns
-        SideLane &sd; hipStream_t st; bool done = false;
-        ~Join() { if (!done) { (void)hipEventRecord(sd.ev_b, sd.s2); (void)hipStreamWaitEvent(st, sd.ev_b, 0); } }
-    } join{side, s};
-    // ---- range A on the caller's stream
-    rc = identify_impl(d_movie, dtype, F, Y, X, box, min_ng, roi4, lo, mid, 0, a.f, a.y, a.x, a.ng, cap, d_na, s);
-    if (rc != PMI_OK) return rc;
-    hipLaunchKernelGGL(lq::lq_rows_a_kernel, dim3(1), dim3(1), 0, s, (const int64_t *)d_na, cap, rows);
-    PMI_HIP(hipEventRecord(side.ev_scan_a, s));
-    rc = pmi_gausslq_movie_dev(d_movie, dtype, F, Y, X, a.f, a.y, a.x, cap, rows + 0, box, baseline, sensitivity, gain, a.th, nullptr,
-                               nullptr, s);
-    if (rc != PMI_OK) return rc;
-    // ---- range B on the side stream, scratch from the inner bank; its scan starts when scan A is done
-    PMI_HIP(hipStreamWaitEvent(side.s2, side.ev_scan_a, 0));
-    const int outer = scratch_enter_inner();
-    Ids b2 = {};
-    rc = scratch(SCR_IDS, ids_bytes, &ptr);
-    if (rc == PMI_OK) {
-        b2 = carve(ptr);
-        rc = identify_impl(d_movie, dtype, F, Y, X, box, min_ng, roi4, mid + 1, hi, 0, b2.f, b2.y, b2.x, b2.ng, cap, d_nb, side.s2);
-    }
-    if (rc == PMI_OK) {
-        hipLaunchKernelGGL(lq::lq_rows_b_kernel, dim3(1), dim3(1), 0, side.s2, (const int64_t *)d_na, (const int64_t *)d_nb, cap, rows, d_out_n);
-        lq::g_lq_stats_second = true;
-        rc = pmi_gausslq_movie_dev(d_movie, dtype, F, Y, X, b2.f, b2.y, b2.x, cap, rows + 1, box, baseline, sensitivity, gain, b2.th,
-                                   nullptr, nullptr, side.s2);
-        lq::g_lq_stats_second = false;
-    }
-    scratch_leave_inner(outer);
-    if (rc != PMI_OK) return rc;
-    PMI_HIP(hipEventRecord(side.ev_b, side.s2));
-    PMI_HIP(hipStreamWaitEvent(s, side.ev_b, 0));
-    join.done = true;
-    hipLaunchKernelGGL(lq::locs_from_fits_lq_kernel, dim3(tblocks), dim3(256), 0, s, a.f, a.y, a.x, a.ng, a.th, cap,
-                       (const int64_t *)(rows + 2), em, cols, (const int64_t *)nullptr);
-    hipLaunchKernelGGL(lq::locs_from_fits_lq_kernel, dim3(tblocks), dim3(256), 0, s, b2.f, b2.y, b2.x, b2.ng, b2.th, cap,
-                       (const int64_t *)(rows + 3), em, cols, (const int64_t *)(rows + 4));
-    PMI_HIP(hipGetLastError());
-    return PMI_OK;
+    };
+    return fused_ranges(fr, 1, F, Y, X, f_lo, f_hi, d_out_n, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -613,13 +613,9 @@ static double g_mle_margin = 0.001;
 // erf / exp of the reference-arithmetic kernel (pmi_mle_set_libm): glibc's bits (libm_glibc.h), the device library's, or
 // glibc's where a result was seen to hang on them (see fit_impl)
 static int g_mle_libm = PMI_LIBM_AUTO;
-// flag statistics of the calling thread's last fit: a device buffer of its own (SCR_STATS of the thread's scratch bank:
-// [0] = spots re-fitted, [1..FLAG_REASONS] = spots flagged per criterion), valid while the scratch generation stands
-static thread_local const unsigned *g_last_stats[2] = {nullptr, nullptr};      // [1]: the second frame range of a fused call
-static thread_local unsigned g_last_stats_generation = 0;
-static thread_local int g_last_stats_device = 0;                                  // the device those buffers live on
-static thread_local int g_last_stats_bank = 0;      // and the scratch bank they were taken from
-static thread_local bool g_stats_second = false;                                  // the fit being queued is that second range
+// flag statistics of the calling thread's last fit (SCR_STATS of the thread's scratch bank: [0] = spots re-fitted,
+// [1..FLAG_REASONS] = spots flagged per criterion)
+static thread_local LastFitStats g_mle_stats;
 
 __global__ void zero_words_kernel(unsigned *__restrict__ a, int na, unsigned *__restrict__ b, int nb)
 {
@@ -655,7 +651,8 @@ static int mle_libm_now()
     return g_mle_libm;
 }
 
-int fit_impl(FitParams p, int method, bool from_movie, hipStream_t s)
+// range: which frame range of a fused call this fit is (1: the second; its statistics add to the first's), 0 otherwise
+int fit_impl(FitParams p, int method, bool from_movie, int range, hipStream_t s)
 {
     if (p.box < 3 || p.box > PMI_MAX_BOX || (p.box & 1) == 0) { set_error("box must be odd, 3..%d (got %d)", PMI_MAX_BOX, p.box); return PMI_ERR_ARG; }
     if (method != PMI_MLE_SIGMA && method != PMI_MLE_SIGMAXY) { set_error("Method not available."); return PMI_ERR_ARG; }
@@ -824,27 +821,15 @@ int fit_impl(FitParams p, int method, bool from_movie, hipStream_t s)
     }
     hipLaunchKernelGGL(flag_stats_kernel, dim3(1), dim3(1), 0, s, flag_counts, mode == PMI_MLE_REFIT ? 2 * nb : 0, stats);
     PMI_HIP(hipGetLastError());
-    g_last_stats[g_stats_second ? 1 : 0] = stats;
-    if (!g_stats_second) g_last_stats[1] = nullptr;
-    g_last_stats_device = current_device();
-    g_last_stats_bank = scratch_user_bank();
-    g_last_stats_generation = scratch_generation_of(g_last_stats_device, g_last_stats_bank, SCR_STATS);
+    if ((rc = g_mle_stats.record(0, range, stats, s)) != PMI_OK) return rc;
     tm.stop();
     return PMI_OK;
 }
 
 static int read_last_stats(unsigned (&h)[16], hipStream_t s)
 {
-    for (unsigned &v : h) v = 0;
-    if (!g_last_stats[0] || g_last_stats_generation != scratch_generation_of(g_last_stats_device, g_last_stats_bank, SCR_STATS)) return PMI_OK;      // no fit yet, or its buffers are gone
-    PMI_HIP(hipStreamSynchronize(s));
-    for (const unsigned *src : g_last_stats) {
-        if (!src) continue;
-        unsigned part[16];
-        PMI_HIP(hipMemcpy(part, src, 64, hipMemcpyDeviceToHost));
-        for (int i = 0; i < 16; i++) h[i] += part[i];
-    }
-    return PMI_OK;
+    if (g_mle_stats.valid()) PMI_HIP(hipStreamSynchronize(s));      // the header promises the caller's stream synchronised
+    return g_mle_stats.read(h);
 }
 
 // ---- get_spots -----------------------------------------------------------
@@ -907,7 +892,7 @@ __global__ void locs_from_fits_kernel(const int32_t *__restrict__ frame, const i
 int identify_impl(const void *d_movie, int dtype, int64_t F, int64_t Y, int64_t X, int box, double min_ng,
                   const int64_t *roi4, int64_t f_lo, int64_t f_hi, int64_t label_offset,
                   int32_t *d_frame, int32_t *d_y, int32_t *d_x, float *d_ng, int64_t cap, int64_t *d_out_n,
-                  hipStream_t s);
+                  bool defer_exact, hipStream_t s);
 
 }  // namespace pmi
 
@@ -971,7 +956,7 @@ int pmi_gaussmle_dev(const float *d_spots, int64_t N, const int64_t *d_n, int bo
     pmi::FitParams p = {};
     p.spots = d_spots; p.N = N; p.d_n = d_n; p.box = box; p.eps = eps; p.max_it = max_it;
     p.thetas = d_thetas; p.crlbs = d_crlbs; p.loglik = d_loglik; p.iterations = d_iterations;
-    return pmi::fit_impl(p, method, false, (hipStream_t)stream);
+    return pmi::fit_impl(p, method, false, 0, (hipStream_t)stream);
 }
 
 int pmi_gaussmle_movie_dev(const void *d_movie, int dtype, int64_t F, int64_t Y, int64_t X,
@@ -987,9 +972,7 @@ int pmi_gaussmle_movie_dev(const void *d_movie, int dtype, int64_t F, int64_t Y,
     p.baseline = (float)baseline; p.sensitivity = (float)sensitivity; p.gain = (float)gain; p.gdiv = pmi::make_const_div((float)gain);
     p.N = N; p.d_n = d_n; p.box = box; p.eps = eps; p.max_it = max_it;
     p.thetas = d_thetas; p.crlbs = d_crlbs; p.loglik = d_loglik; p.iterations = d_iterations;
-    // a fused call whose scan handed the pixels on (these identifications, this thread, just now)
-    if (pmi::g_handoff.used && pmi::g_handoff.d_slot && dtype == PMI_U16) { p.pix = pmi::g_handoff.pix; p.slot = pmi::g_handoff.d_slot; }
-    return pmi::fit_impl(p, method, true, (hipStream_t)stream);
+    return pmi::fit_impl(p, method, true, 0, (hipStream_t)stream);
 }
 
 int pmi_gaussmle(const float *spots, int64_t N, int box, double eps, int max_it, int method, float *thetas,
@@ -1100,12 +1083,8 @@ int pmi_locs_from_fits_dev(const int32_t *d_frame, const int32_t *d_y, const int
     return PMI_OK;
 }
 
-// ---- two frame ranges in flight ---------------------------------------------------------------------------------
-// The scan is bound by memory requests, the fit by VALU issue: the scan of frame range B beside the fit of range A
-// takes less than the two one after the other.  pmi_localize_mle_dev therefore cuts its frames
-// in two: stream s runs scan A, fit A; a side stream of the library runs scan B (started when scan A is done) and
-// fit B, with scratch from the inner bank; the table rows are written once both counts are known (A's rows, then
-// B's), so the capacity contract holds for the sum.
+// ---- the fused call ---------------------------------------------------------------------------------------------
+// identify -> fit -> table, in one or two frame ranges (fused_ranges, runtime.hip).
 //
 // Deferred exact stage (default, pmi_localize_set_defer): on uint16 / uint8 / int16 movies and boxes up to 7x7
 // the packed scan only emits CANDIDATES (window maximum, floor, neighbour rule) and the fit's start-value kernel, which
@@ -1116,51 +1095,8 @@ int pmi_locs_from_fits_dev(const int32_t *d_frame, const int32_t *d_y, const int
 // that: *d_out_n reports their number (an upper bound of the rows), nothing is fitted, the table is untouched — the same
 // contract as a table that is too small.
 namespace pmi {
-static bool g_localize_handoff = false;
 static bool g_localize_defer = true;
-
-// rows: [0] rows of A to fit, [1] rows of B to fit, [2] rows of A for the table, [3] rows of B for the table, [4] row offset of B
-__global__ void range_rows_a_kernel(const int64_t *__restrict__ n_a, int64_t cap, int64_t *__restrict__ rows)
-{
-    rows[0] = *n_a > cap ? 0 : *n_a;
-}
-__global__ void range_rows_b_kernel(const int64_t *__restrict__ n_a, const int64_t *__restrict__ n_b, int64_t cap,
-                                    int64_t *__restrict__ rows, int64_t *__restrict__ d_out_n)
-{
-    const int64_t a = *n_a, b = *n_b, total = a + b;
-    const bool fits = total <= cap;
-    rows[1] = fits ? b : 0;
-    rows[2] = fits ? a : 0;
-    rows[3] = fits ? b : 0;
-    rows[4] = a;
-    *d_out_n = total;
-}
-// deferred exact stage: the candidates of a range that may be fitted (all of them, or none when they overflow capc)
-__global__ void cand_rows_kernel(const int64_t *__restrict__ n_cand, int64_t capc, int64_t *__restrict__ rows_fit)
-{
-    *rows_fit = *n_cand > capc ? 0 : *n_cand;
-}
-// ... and the table rows once the accepted candidates are counted (acc_b == nullptr: one range)
-__global__ void accepted_rows_kernel(const int64_t *__restrict__ cand_a, const unsigned *__restrict__ acc_a,
-                                     const int64_t *__restrict__ cand_b, const unsigned *__restrict__ acc_b, int64_t capc,
-                                     int64_t cap, int64_t *__restrict__ rows, int64_t *__restrict__ d_out_n)
-{
-    const int64_t ca = *cand_a, cb = cand_b ? *cand_b : 0;
-    const bool overflow = ca > capc || cb > capc;
-    const int64_t a = overflow ? 0 : (int64_t)*acc_a, b = (overflow || !acc_b) ? 0 : (int64_t)*acc_b;
-    const bool fits = !overflow && a + b <= cap;
-    rows[2] = fits ? a : 0;
-    rows[3] = fits ? b : 0;
-    rows[4] = a;
-    *d_out_n = overflow ? ca + cb : a + b;
-}
 }  // namespace pmi
-
-int pmi_localize_set_handoff(int on)
-{
-    pmi::g_localize_handoff = on != 0;
-    return PMI_OK;
-}
 
 int pmi_localize_set_defer(int on)
 {
@@ -1183,12 +1119,6 @@ int pmi_localize_mle_dev(const void *d_movie, int dtype, int64_t F, int64_t Y, i
     using namespace pmi;
     if (cap <= 0) { set_error("capacity must be positive"); return PMI_ERR_ARG; }
     if (dtype < 0 || dtype > PMI_F32) { set_error("unknown dtype code %d", dtype); return PMI_ERR_ARG; }
-    hipStream_t s = (hipStream_t)stream;
-    void *cols[PMI_LOC_COLUMNS];
-    for (int c = 0; c < PMI_LOC_COLUMNS; c++) cols[c] = (char *)d_table + (size_t)c * cap * 4;
-    // pixel hand-off from the scan's exact stage to the fit (uint16 movies, boxes of the row-per-lane fit): room for twice
-    // the table's rows (candidates that fail the threshold take a slot too), spread over the eight record shards
-    const bool hand = g_localize_handoff && dtype == PMI_U16 && box <= 15 && mle_mode_now() != PMI_MLE_STRICT;
     // the exact stage of identify in the fit's start-value kernel instead of the scan (see above)
     // (boxes up to 7: eight lanes per candidate in the start-value kernel.  With the 16-lane groups of boxes 9 ... 15 the stage
     // costs the fit more than it saves the scan — config 5, box 13: scan 7.0 -> 6.0 ms, fit 19.9 -> 22.0 ms — so those boxes
@@ -1196,156 +1126,65 @@ int pmi_localize_mle_dev(const void *d_movie, int dtype, int64_t F, int64_t Y, i
     // (a tuning build's PMI_FIT_WAVE_PER_SPOT / PMI_MLE_NO_KEEP take the fit off the row-per-lane path that hosts the stage:
     // the stage then stays in the scan — the predicate fit_impl checks)
     static const bool off_g8 = tuning_env("PMI_FIT_WAVE_PER_SPOT") != nullptr || tuning_env("PMI_MLE_NO_KEEP") != nullptr;
-    const bool defer = g_localize_defer && !hand && !off_g8 && box <= 7 && mle_mode_now() != PMI_MLE_STRICT &&
+    const bool defer = g_localize_defer && !off_g8 && box <= 7 && mle_mode_now() != PMI_MLE_STRICT &&
                        (dtype == PMI_U16 || dtype == PMI_U8 || dtype == PMI_I16) && min_ng > 0.0 && std::isfinite(min_ng);
     const int64_t capc = defer ? cap + cap / 2 + 4096 : cap;         // rows of the identification / fit arrays
     int64_t cy0 = 0, cx0 = 0, cy1 = Y, cx1 = X;
     if (roi4) { cy0 = roi4[0]; cx0 = roi4[1]; cy1 = roi4[2]; cx1 = roi4[3]; }
-    struct Ids { int32_t *f, *y, *x; float *ng, *th, *cr, *ll; int32_t *it, *slot, *tlist; unsigned *blk; unsigned char *acc; };
+    struct Ids { int32_t *f, *y, *x; float *ng, *th, *cr, *ll; int32_t *it, *tlist; unsigned *blk; unsigned char *acc; };
     const size_t acc_blocks = (size_t)((capc + ACC_BLOCK - 1) / ACC_BLOCK) + 2;
-    auto carve = [&](void *ptr) {
+    const int nblk_c = (int)((capc + ACC_BLOCK - 1) / ACC_BLOCK);
+    auto carve = [=](void *ptr) {
         Ids d;
         d.f = (int32_t *)ptr; d.y = d.f + capc; d.x = d.y + capc;
         d.ng = (float *)(d.x + capc);
         d.th = d.ng + capc; d.cr = d.th + capc * 6; d.ll = d.cr + capc * 6;
         d.it = (int32_t *)(d.ll + capc);
-        d.slot = d.it + capc;
-        d.tlist = d.slot + capc;
+        d.tlist = d.it + capc;
         d.blk = (unsigned *)(d.tlist + capc);
         d.acc = (unsigned char *)(d.blk + acc_blocks);
         return d;
     };
-    const size_t ids_bytes = (size_t)capc * (16 + 16 * 4 + 1) + acc_blocks * sizeof(unsigned) + 16;
-    const unsigned pix_cap = (unsigned)std::min<int64_t>(std::max<int64_t>(cap / 4, 4096), 0x0fffffff);
-    const size_t pix_bytes = (size_t)8 * pix_cap * (size_t)(box * (box / 2 + 1)) * sizeof(uint32_t);
-    auto arm_handoff = [&](int32_t *d_slot) -> int {         // in the scratch bank that is current
-        g_handoff = PixHandoff();
-        if (!hand) return PMI_OK;
-        void *pp = nullptr;
-        int r = scratch(SCR_PIX, pix_bytes, &pp);
-        if (r != PMI_OK) return r;
-        g_handoff.pix = (uint32_t *)pp; g_handoff.cap_per_shard = pix_cap; g_handoff.d_slot = d_slot;
-        return PMI_OK;
+    LocCols lc;
+    for (int c = 0; c < PMI_LOC_COLUMNS; c++) lc.c[c] = (char *)d_table + (size_t)c * cap * 4;
+    FusedRanges fr;
+    fr.ids_bytes = (size_t)capc * (16 + 15 * 4 + 1) + acc_blocks * sizeof(unsigned) + 16;
+    fr.capc = capc;
+    fr.cap = cap;
+    fr.rejects = defer;
+    // identify (candidates when deferred) over frames [lo, hi]
+    fr.scan = [&](void *ids, int64_t lo, int64_t hi, int64_t *d_cnt, hipStream_t st) {
+        const Ids d = carve(ids);
+        return identify_impl(d_movie, dtype, F, Y, X, box, min_ng, roi4, lo, hi, 0, d.f, d.y, d.x, d.ng, capc, d_cnt, defer, st);
     };
-    // identify (candidates when deferred) over frames [lo_, hi_] into d, count at d_cnt
-    auto scan_range = [&](const Ids &d, int64_t lo_, int64_t hi_, int64_t *d_cnt, hipStream_t st) -> int {
-        g_defer_exact = defer;
-        const int r = identify_impl(d_movie, dtype, F, Y, X, box, min_ng, roi4, lo_, hi_, 0, d.f, d.y, d.x, d.ng, capc, d_cnt, st);
-        g_defer_exact = false;
-        return r;
-    };
-    // the fit of the rows *d_rows of d (with the exact stage of identify in its start-value kernel when deferred)
-    auto fit_range = [&](const Ids &d, const int64_t *d_rows, hipStream_t st) -> int {
+    // the fit of the rows *d_rows (with the exact stage of identify in its start-value kernel when deferred)
+    fr.fit = [&](void *ids, const int64_t *d_rows, int range, hipStream_t st) {
+        const Ids d = carve(ids);
         FitParams p = {};
         p.movie = d_movie; p.dtype = dtype; p.Y = Y; p.X = X; p.frame = d.f; p.y = d.y; p.x = d.x;
         p.baseline = (float)baseline; p.sensitivity = (float)sensitivity; p.gain = (float)gain; p.gdiv = make_const_div((float)gain);
         p.N = capc; p.d_n = d_rows; p.box = box; p.eps = eps; p.max_it = max_it;
         p.thetas = d.th; p.crlbs = d.cr; p.loglik = d.ll; p.iterations = d.it;
-        if (g_handoff.used && g_handoff.d_slot && dtype == PMI_U16) { p.pix = g_handoff.pix; p.slot = g_handoff.d_slot; }
         if (defer) {
             p.ng_io = d.ng; p.accept = d.acc; p.min_ng = min_ng;
             p.crop_y0 = (int)cy0; p.crop_x0 = (int)cx0; p.crop_cy = (int)(cy1 - cy0); p.crop_cx = (int)(cx1 - cx0);
             p.alist_out = d.tlist; p.alist_blk_out = d.blk;
         }
-        int r = fit_impl(p, method, true, st);
+        int r = fit_impl(p, method, true, range, st);
         if (r != PMI_OK || !defer) return r;
         // the table's source rows (total at blk[nblk]): the list the fit made for its only batch, or one pass over all flags
         if (capc <= FIT_BATCH) return PMI_OK;
         return build_accept_list(d.acc, 0, capc, d_rows, d.blk, d.tlist, st);
     };
-    const unsigned *const no_acc = nullptr;
-    const int nblk_c = (int)((capc + ACC_BLOCK - 1) / ACC_BLOCK);
-    LocCols lc;
-    for (int c = 0; c < PMI_LOC_COLUMNS; c++) lc.c[c] = cols[c];
-    const unsigned tblocks = (unsigned)((cap + 255) / 256);
-
-    const int64_t lo = f_lo < 0 ? 0 : f_lo, hi = f_hi > F - 1 ? F - 1 : f_hi, nf = hi - lo + 1;
-    // two ranges pay when each keeps the chip busy for a while (below ~1e8 pixels a range is a few tens of microseconds)
-    const bool two = g_localize_ranges == 2 && !g_kernel_timing && nf >= 16 && (double)nf * (double)Y * (double)X >= 2.5e8;
-    void *ptr = nullptr, *cptr = nullptr;
-    int rc;
-    if ((rc = scratch(SCR_ROWS, 8 * sizeof(int64_t), &cptr)) != PMI_OK) return rc;
-    int64_t *d_na = (int64_t *)cptr, *d_nb = d_na + 1, *rows = d_na + 2;
-    if (!two) {
-        if ((rc = scratch(SCR_IDS, ids_bytes, &ptr)) != PMI_OK) return rc;
-        const Ids d = carve(ptr);
-        if ((rc = arm_handoff(d.slot)) != PMI_OK) return rc;
-        int64_t *d_cnt = defer ? d_na : d_out_n;
-        rc = scan_range(d, f_lo, f_hi, d_cnt, s);
-        if (rc != PMI_OK) { g_handoff = PixHandoff(); return rc; }
-        hipLaunchKernelGGL(cand_rows_kernel, dim3(1), dim3(1), 0, s, (const int64_t *)d_cnt, capc, rows + 0);
-        rc = fit_range(d, rows + 0, s);
-        g_handoff = PixHandoff();
-        if (rc != PMI_OK) return rc;
-        if (defer) {
-            hipLaunchKernelGGL(accepted_rows_kernel, dim3(1), dim3(1), 0, s, (const int64_t *)d_na, (const unsigned *)(d.blk + nblk_c),
-                               (const int64_t *)nullptr, no_acc, capc, cap, rows, d_out_n);
-            hipLaunchKernelGGL(locs_from_fits_kernel, dim3(tblocks), dim3(256), 0, s, d.f, d.y, d.x, d.ng, d.th, d.cr, d.ll, d.it, cap,
-                               (const int64_t *)(rows + 2), box, lc, (const int64_t *)nullptr, (const int32_t *)d.tlist);
-        } else {
-            hipLaunchKernelGGL(locs_from_fits_kernel, dim3(tblocks), dim3(256), 0, s, d.f, d.y, d.x, d.ng, d.th, d.cr, d.ll, d.it, cap,
-                               (const int64_t *)(rows + 0), box, lc, (const int64_t *)nullptr, (const int32_t *)nullptr);
-        }
+    fr.accepted = [&](void *ids) { return (const unsigned *)(carve(ids).blk + nblk_c); };
+    fr.table = [&](void *ids, const int64_t *d_rows, const int64_t *d_row0, hipStream_t st) {
+        const Ids d = carve(ids);
+        hipLaunchKernelGGL(locs_from_fits_kernel, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, st, d.f, d.y, d.x, d.ng, d.th,
+                           d.cr, d.ll, d.it, cap, d_rows, box, lc, d_row0, (const int32_t *)(defer ? d.tlist : nullptr));
         PMI_HIP(hipGetLastError());
         return PMI_OK;
-    }
-    SideLane *side_p = nullptr;
-    if ((rc = side_lane(0, &side_p)) != PMI_OK) return rc;
-    SideLane &side = *side_p;
-    const int64_t mid = lo + nf / 2 - 1;                      // A = [lo, mid], B = [mid + 1, hi]
-    // counts of the two ranges and the row bookkeeping live in the OUTER bank (both streams read them)
-    if ((rc = scratch(SCR_IDS, ids_bytes, &ptr)) != PMI_OK) return rc;
-    const Ids a = carve(ptr);
-    PMI_HIP(hipEventRecord(side.ev_start, s));               // the side stream joins the caller's stream order here
-    PMI_HIP(hipStreamWaitEvent(side.s2, side.ev_start, 0));
-    // From here on work may be queued on the side stream: whatever happens, the caller's stream is ordered after it
-    // before this call returns (a caller that frees or reuses its buffers on an error must not race kernels on s2).
-    struct Join {
-        SideLane &sd; hipStream_t st; bool done = false;
-        ~Join() { if (!done) { (void)hipEventRecord(sd.ev_b, sd.s2); (void)hipStreamWaitEvent(st, sd.ev_b, 0); } }
-    } join{side, s};
-    // ---- range A on the caller's stream
-    if ((rc = arm_handoff(a.slot)) != PMI_OK) return rc;
-    rc = scan_range(a, lo, mid, d_na, s);
-    if (rc != PMI_OK) { g_handoff = PixHandoff(); return rc; }
-    hipLaunchKernelGGL(range_rows_a_kernel, dim3(1), dim3(1), 0, s, (const int64_t *)d_na, capc, rows);
-    PMI_HIP(hipEventRecord(side.ev_scan_a, s));
-    rc = fit_range(a, rows + 0, s);
-    g_handoff = PixHandoff();
-    if (rc != PMI_OK) return rc;
-    // ---- range B on the side stream, scratch from the inner bank; its scan starts when scan A is done
-    PMI_HIP(hipStreamWaitEvent(side.s2, side.ev_scan_a, 0));
-    const int outer = scratch_enter_inner();
-    Ids b2 = {};
-    rc = scratch(SCR_IDS, ids_bytes, &ptr);
-    if (rc == PMI_OK) {
-        b2 = carve(ptr);
-        rc = arm_handoff(b2.slot);
-    }
-    if (rc == PMI_OK) rc = scan_range(b2, mid + 1, hi, d_nb, side.s2);
-    if (rc == PMI_OK) {
-        if (defer) hipLaunchKernelGGL(cand_rows_kernel, dim3(1), dim3(1), 0, side.s2, (const int64_t *)d_nb, capc, rows + 1);
-        else hipLaunchKernelGGL(range_rows_b_kernel, dim3(1), dim3(1), 0, side.s2, (const int64_t *)d_na, (const int64_t *)d_nb, cap, rows, d_out_n);
-        g_stats_second = true;
-        rc = fit_range(b2, rows + 1, side.s2);
-        g_stats_second = false;
-    }
-    g_handoff = PixHandoff();
-    scratch_leave_inner(outer);
-    if (rc != PMI_OK) return rc;
-    PMI_HIP(hipEventRecord(side.ev_b, side.s2));
-    PMI_HIP(hipStreamWaitEvent(s, side.ev_b, 0));
-    join.done = true;
-    // ---- the table, once both counts are known: A's rows, then B's
-    if (defer)
-        hipLaunchKernelGGL(accepted_rows_kernel, dim3(1), dim3(1), 0, s, (const int64_t *)d_na, (const unsigned *)(a.blk + nblk_c),
-                           (const int64_t *)d_nb, (const unsigned *)(b2.blk + nblk_c), capc, cap, rows, d_out_n);
-    hipLaunchKernelGGL(locs_from_fits_kernel, dim3(tblocks), dim3(256), 0, s, a.f, a.y, a.x, a.ng, a.th, a.cr, a.ll, a.it, cap,
-                       (const int64_t *)(rows + 2), box, lc, (const int64_t *)nullptr, (const int32_t *)(defer ? a.tlist : nullptr));
-    hipLaunchKernelGGL(locs_from_fits_kernel, dim3(tblocks), dim3(256), 0, s, b2.f, b2.y, b2.x, b2.ng, b2.th, b2.cr, b2.ll, b2.it, cap,
-                       (const int64_t *)(rows + 3), box, lc, (const int64_t *)(rows + 4), (const int32_t *)(defer ? b2.tlist : nullptr));
-    PMI_HIP(hipGetLastError());
-    return PMI_OK;
+    };
+    return fused_ranges(fr, 0, F, Y, X, f_lo, f_hi, d_out_n, (hipStream_t)stream);
 }
 
 }  // extern "C"

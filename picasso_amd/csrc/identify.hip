@@ -154,7 +154,7 @@ __global__ __launch_bounds__(ID_NT) void identify_scan_kernel(
                 Record rec;
                 rec.frame = (int32_t)(p.f_lo + fi + p.frame_label_offset);
                 rec.yx = pack_yx(ty * ID_TH + rr + p.y0, tx * ID_TW + cc + p.x0);
-                rec.slot = -1;
+                rec.pad = 0;
                 rec.ng = ng;
                 recs[(long long)shard * cap + pos] = rec;
             }
@@ -248,8 +248,7 @@ __global__ __launch_bounds__(SORT_THREADS) void sort_in_frame_kernel(const Recor
                                                                      const unsigned long long *__restrict__ counters,
                                                                      long long cap,
                                                                      int32_t *__restrict__ o_frame, int32_t *__restrict__ o_y,
-                                                                     int32_t *__restrict__ o_x, float *__restrict__ o_ng,
-                                                                     int32_t *__restrict__ o_slot)
+                                                                     int32_t *__restrict__ o_x, float *__restrict__ o_ng)
 {
     using key_t = typename std::conditional<K32, unsigned, unsigned long long>::type;
     __shared__ __attribute__((aligned(16))) key_t s_key[SORT_LDS];
@@ -302,7 +301,6 @@ __global__ __launch_bounds__(SORT_THREADS) void sort_in_frame_kernel(const Recor
             o_y[b + rank] = (int32_t)(r.yx >> 16);
             o_x[b + rank] = (int32_t)(r.yx & 0xffffu);
             o_ng[b + rank] = r.ng;
-            if (o_slot) o_slot[b + rank] = r.slot;
         }
     }
 }
@@ -361,8 +359,7 @@ static int launch_scan(const void *d_movie, const IdParams &p, const float *d_ta
 int launch_scan_u16_fast(const void *d_movie, int dtype, int64_t Y, int64_t X, int y0, int x0, int cy, int cx, int64_t f_lo,
                          int64_t label_off, int nframes, int box, double min_ng, const float *d_tab, Record *recs,
                          long long cap, unsigned long long *n_total, int *frame_count, hipStream_t s, bool *handled,
-                         const int *gate = nullptr, uint32_t *pix = nullptr, unsigned *pix_cnt = nullptr, unsigned pix_cap = 0,
-                         bool defer = false, const float *fmovie = nullptr, int gate_want = 0);
+                         const int *gate = nullptr, bool defer = false, const float *fmovie = nullptr, int gate_want = 0);
 
 // float32 / int32 / uint32 movies that hold 16-bit counts (a camera's counts saved wide): the frames are narrowed to
 // uint16 — exactly, or not at all: any pixel that is not an integer in 0..65535 raises the chunk's flag — and take the
@@ -407,11 +404,12 @@ __global__ __launch_bounds__(256) void narrow_to_u16_kernel(const T *__restrict_
 // is decided on the float32 pixels.
 
 // d_movie points at frame 0 of a stack holding at least frames [f_lo, f_hi].
-// Labels written = frame index + label_offset.
+// Labels written = frame index + label_offset.  defer_exact (a fused MLE call): the packed scan may leave its exact stage to
+// the fit's start-value kernel and emit candidates (NG_DEFERRED_BITS, pmi_common.h).
 int identify_impl(const void *d_movie, int dtype, int64_t F, int64_t Y, int64_t X, int box, double min_ng,
                   const int64_t *roi4, int64_t f_lo, int64_t f_hi, int64_t label_offset,
                   int32_t *d_frame, int32_t *d_y, int32_t *d_x, float *d_ng, int64_t cap, int64_t *d_out_n,
-                  hipStream_t s)
+                  bool defer_exact, hipStream_t s)
 {
     if (box < 3 || box > PMI_MAX_BOX || (box & 1) == 0) { set_error("box must be odd, 3..%d (got %d)", PMI_MAX_BOX, box); return PMI_ERR_ARG; }
     if (F < 0 || Y <= 0 || X <= 0 || Y > 65535 || X > 65535) { set_error("bad movie shape (%lld,%lld,%lld)", (long long)F, (long long)Y, (long long)X); return PMI_ERR_ARG; }
@@ -429,9 +427,7 @@ int identify_impl(const void *d_movie, int dtype, int64_t F, int64_t Y, int64_t 
     int rc;
     if ((rc = scratch(SCR_COUNTERS, 256, &ptr)) != PMI_OK) return rc;
     d_total = (unsigned long long *)ptr;
-    unsigned *pix_cnt = (unsigned *)((char *)ptr + 128);              // slot counters of the pixel hand-off, one per shard
     PMI_HIP(hipMemsetAsync(d_total, 0, 256, s));
-    g_handoff.used = false;
     if (nf <= 0 || cy < box + 1 || cx < box + 1) {   // no interior pixel can be scanned
         PMI_HIP(hipMemsetAsync(d_out_n, 0, sizeof(int64_t), s));
         return PMI_OK;
@@ -460,12 +456,9 @@ int identify_impl(const void *d_movie, int dtype, int64_t F, int64_t Y, int64_t 
         bool fast = false;
         rc = PMI_OK;
         // register-pipelined packed-u16 scan (identify_fast.hip: uint16, uint8, int16) when the layout allows
-        // (a fused call may leave the exact stage to its fit's start-value kernel: g_defer_exact, pmi_common.h)
-        const bool hand = g_handoff.pix && dtype == PMI_U16 && !g_defer_exact;
+        // (a fused call may leave the exact stage to its fit's start-value kernel: defer_exact)
         rc = launch_scan_u16_fast(d_movie, dtype, Y, X, p.y0, p.x0, p.cy, p.cx, f_lo, label_offset, p.nframes, box, min_ng,
-                                      d_tab, recs, cap, d_total, count, s, &fast, nullptr, hand ? g_handoff.pix : nullptr,
-                                      hand ? pix_cnt : nullptr, hand ? g_handoff.cap_per_shard : 0u, g_defer_exact);
-        g_handoff.used = hand && fast;
+                                      d_tab, recs, cap, d_total, count, s, &fast, nullptr, defer_exact);
         p.gate = nullptr;
         const bool wide = dtype == PMI_U32 || dtype == PMI_I32 || dtype == PMI_F32;
         static const bool no_narrow = tuning_env("PMI_IDENTIFY_NO_NARROW") != nullptr;
@@ -476,8 +469,7 @@ int identify_impl(const void *d_movie, int dtype, int64_t F, int64_t Y, int64_t 
             // 32-bit integer movies (round 6): the same scan with the reference's cast to float32 (localize.py:332) in front
             // of the keys and of every exact read; frames too narrow for one row range per lane set keep the routes below.
             rc = launch_scan_u16_fast(d_movie, dtype, Y, X, p.y0, p.x0, p.cy, p.cx, f_lo, label_offset, p.nframes, box, min_ng,
-                                      d_tab, recs, cap, d_total, count, s, &fast, nullptr, nullptr, nullptr, 0u, false,
-                                      (const float *)d_movie, 0);
+                                      d_tab, recs, cap, d_total, count, s, &fast, nullptr, false, (const float *)d_movie, 0);
         }
         if (rc == PMI_OK && !fast && wide && !no_narrow && ((uintptr_t)d_movie & 15) == 0 && ((Y * X) & 3) == 0) {
             // chunks of frames through a uint16 copy of at most 1 GiB
@@ -509,8 +501,7 @@ int identify_impl(const void *d_movie, int dtype, int64_t F, int64_t Y, int64_t 
                     // loads them; exact decisions on the float32 pixels
                     bool f3 = false;
                     rc = launch_scan_u16_fast(srcp, PMI_F32, Y, X, p.y0, p.x0, p.cy, p.cx, 0, f_lo + label_offset + c0, (int)n, box, min_ng,
-                                              d_tab, recs, cap, d_total, count + c0, s, &f3, gates + ci, nullptr, nullptr, 0u, false,
-                                              (const float *)srcp, 1);
+                                              d_tab, recs, cap, d_total, count + c0, s, &f3, gates + ci, false, (const float *)srcp, 1);
                     if (rc != PMI_OK) return rc;
                     if (f3) continue;
                 }
@@ -546,10 +537,10 @@ int identify_impl(const void *d_movie, int dtype, int64_t F, int64_t Y, int64_t 
         const unsigned split = (unsigned)std::min<int64_t>(16, std::max<int64_t>(1, (Y * X + 262143) / 262144));
         if (Y <= 65536 && X <= 65536)
             hipLaunchKernelGGL(sort_in_frame_kernel<true>, dim3((unsigned)nf, split), dim3(SORT_THREADS), 0, s, grouped, base,
-                               count, d_total, (long long)cap, d_frame, d_y, d_x, d_ng, g_handoff.d_slot);
+                               count, d_total, (long long)cap, d_frame, d_y, d_x, d_ng);
         else
             hipLaunchKernelGGL(sort_in_frame_kernel<false>, dim3((unsigned)nf, split), dim3(SORT_THREADS), 0, s, grouped, base,
-                               count, d_total, (long long)cap, d_frame, d_y, d_x, d_ng, g_handoff.d_slot);
+                               count, d_total, (long long)cap, d_frame, d_y, d_x, d_ng);
     }
     PMI_HIP(hipGetLastError());
     return PMI_OK;
@@ -601,7 +592,7 @@ int pmi_identify_dev(const void *d_movie, int dtype, int64_t F, int64_t Y, int64
                      int32_t *d_x, float *d_ng, int64_t cap, int64_t *d_out_n, void *stream)
 {
     return pmi::identify_impl(d_movie, dtype, F, Y, X, box, min_ng, roi4, f_lo, f_hi, 0, d_frame, d_y, d_x, d_ng,
-                              cap, d_out_n, (hipStream_t)stream);
+                              cap, d_out_n, false, (hipStream_t)stream);
 }
 
 static size_t dtype_size(int dtype)
@@ -643,7 +634,7 @@ int pmi_identify(const void *movie, int dtype, int64_t F, int64_t Y, int64_t X, 
         PMI_HIP(hipMemcpy(d_chunk, (const char *)movie + (size_t)c0 * frame_bytes, (size_t)nfc * frame_bytes, hipMemcpyHostToDevice));
         int64_t room = overflow ? 0 : std::max<int64_t>(cap - total, 0);
         rc = identify_impl(d_chunk, dtype, nfc, Y, X, box, min_ng, roi4, 0, nfc - 1, c0, d_frame, d_y, d_x, d_ng,
-                           room, d_n, nullptr);
+                           room, d_n, false, nullptr);
         if (rc != PMI_OK) return rc;
         int64_t n = 0;
         PMI_HIP(hipMemcpy(&n, d_n, sizeof(n), hipMemcpyDeviceToHost));

@@ -6,6 +6,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <functional>
+
 #include "../../include/picasso_hip.h"
 
 #define PMI_WAVE 64
@@ -54,7 +56,6 @@ enum ScratchSlot {
     SCR_ROWS,             // rows the fit stages of the fused pipelines may touch
     SCR_NARROW,           // uint16 copy of a chunk of a 32-bit movie (identify)
     SCR_GATES,            // per-chunk flags of that copy
-    SCR_PIX,              // box pixels of the candidates, left by the scan's exact stage for the fit (identify_fast.hip)
     SCR_STATS,            // flag statistics of the last MLE fit (re-fit count, count per criterion)
     SCR_LQ_STATS,         // the same of the last least-squares fit (spots fitted again, count per reason)
     SCR_NUM
@@ -73,14 +74,41 @@ int scratch_user_bank();                    // the bank pmi_scratch_bank selecte
 // one device and bank are serialised by the caller (picasso_amd/_lib.py lock()), as for the scratch buffers.
 struct SideLane { hipStream_t s2 = nullptr; hipEvent_t ev_start = nullptr, ev_scan_a = nullptr, ev_b = nullptr, stats_done[2] = {nullptr, nullptr}; };
 int side_lane(int pipeline, SideLane **lane);
-// Fused pipelines: *d_rows = *d_total if it fits the caller's capacity, else 0 (the identification columns were not
-// written; the caller sees *d_total > cap and resubmits), so that the fit stages never follow stale rows.
-int rows_to_fit(const int64_t *d_total, int64_t cap, const int64_t **d_rows, hipStream_t s);
+
+// Statistics of the calling thread's last fit of one pipeline (0: MLE, SCR_STATS: [0] spots re-fitted, [1..] spots flagged per
+// criterion; 1: least squares, SCR_LQ_STATS: [0] spots fitted again, [1..8] why): a 64-byte device buffer per frame range of
+// the call, read behind the event recorded after its statistics kernel (the stream the fit ran on may be gone by then) and
+// only while the scratch generation it was taken from stands.
+struct LastFitStats {
+    int device = 0, bank = 0, slot = 0;
+    unsigned generation = 0;
+    const unsigned *buf[2] = {nullptr, nullptr};     // [1]: the second frame range of a fused call
+    hipEvent_t done[2] = {nullptr, nullptr};         // the events belong to the device's side lane, not to this thread
+    // after the statistics kernel of frame range `range` (0: a whole call, or the first range) is queued on s
+    int record(int pipeline, int range, const unsigned *stats, hipStream_t s);
+    bool valid() const;
+    int read(unsigned (&h)[16]) const;               // the ranges' sums; zeros when there is no fit or its buffers are gone
+};
+
+// The schedule of the fused calls (pmi_localize_mle_dev, pmi_localize_lq_dev): identify, fit, table, with the frames cut in
+// two ranges when that pays (runtime.hip).  The caller supplies its parts; `ids` is one range's SCR_IDS buffer of ids_bytes.
+struct FusedRanges {
+    size_t ids_bytes;
+    int64_t capc;          // rows of a range's identification / fit arrays: the candidates it may hold
+    int64_t cap;           // rows of the table
+    bool rejects;          // the fit may reject candidates: `accepted` counts those it kept (else accepted == candidates)
+    std::function<int(void *ids, int64_t f_lo, int64_t f_hi, int64_t *d_cnt, hipStream_t st)> scan;
+    std::function<int(void *ids, const int64_t *d_rows, int range, hipStream_t st)> fit;
+    std::function<const unsigned *(void *ids)> accepted;
+    std::function<int(void *ids, const int64_t *d_rows, const int64_t *d_row0, hipStream_t st)> table;
+};
+int fused_ranges(const FusedRanges &c, int pipeline, int64_t F, int64_t Y, int64_t X, int64_t f_lo, int64_t f_hi,
+                 int64_t *d_out_n, hipStream_t s);
 
 struct Record {   // one identification, 16 B
     int32_t frame;
     uint32_t yx;      // y << 16 | x (frames are at most 65535 x 65535 on this path)
-    int32_t slot;     // where the exact stage of the scan left the spot's pixels (identify_fast.hip), -1: nowhere
+    int32_t pad;      // 0: keeps a record one 16-byte store
     float ng;
 };
 __host__ __device__ __forceinline__ uint32_t pack_yx(int y, int x) { return ((uint32_t)y << 16) | (uint32_t)(x & 0xffff); }
@@ -89,8 +117,6 @@ __host__ __device__ __forceinline__ uint32_t pack_yx(int y, int x) { return ((ui
 // rows it needs: the scan then emits CANDIDATES whose net gradient is this NaN pattern (an accepted identification's
 // net gradient is never NaN: it passed `ng > min_ng`), and the start-value kernel decides them (gaussmle_g8.hip).
 constexpr uint32_t NG_DEFERRED_BITS = 0x7fc0d1feu;
-// set (per thread) by a fused call around identify_impl: the packed scan may defer its exact stage
-extern thread_local bool g_defer_exact;
 // the scan kernel the calling thread launched last, as rocprofv3 names it (+ " defer" when it may leave its exact stage to
 // the fit): pmi_last_scan_kernel, so that a benchmark can tell which kernel a committed counter file belongs to
 extern thread_local char g_last_scan_kernel[128];
@@ -99,16 +125,6 @@ extern int g_localize_ranges;        // frame ranges a fused call keeps in fligh
 // pixel load as float32 (the reference's np.float32(frame), localize.py:332)
 template <typename T>
 __device__ __forceinline__ float px_f32(const T *p, int64_t i) { return (float)p[i]; }
-
-// Pixel hand-off from identify to the fit: a fused call sets this (per thread) around identify_impl; the packed uint16
-// scan then leaves every candidate's box rows at pix[slot] and the ordered identifications carry their slot.
-struct PixHandoff {
-    uint32_t *pix = nullptr;        // shards x cap_per_shard slots of box * (box / 2 + 1) uint32 (packed uint16 pairs)
-    unsigned cap_per_shard = 0;
-    int32_t *d_slot = nullptr;      // out: slot of every identification (-1: none), ordered like d_frame / d_y / d_x
-    bool used = false;              // out: the scan that ran could fill it
-};
-extern thread_local PixHandoff g_handoff;
 
 struct KernelTimes { float scan_ms, fit_ms; };
 extern bool g_kernel_timing;

@@ -10,8 +10,6 @@ namespace pmi {
 static thread_local char g_err[512] = "";
 bool g_kernel_timing = false;
 KernelTimes g_last_times = {0.f, 0.f};
-thread_local PixHandoff g_handoff;
-thread_local bool g_defer_exact = false;
 int g_localize_ranges = 2;          // pmi_localize_set_ranges (gaussmle.hip); read by both fused calls
 thread_local char g_last_scan_kernel[128] = "";
 
@@ -152,20 +150,131 @@ int side_lane(int pipeline, SideLane **lane)
     return PMI_OK;
 }
 
-__global__ void rows_to_fit_kernel(const int64_t *__restrict__ total, int64_t cap, int64_t *__restrict__ rows)
+int LastFitStats::record(int pipeline, int range, const unsigned *stats, hipStream_t s)
 {
-    const int64_t n = *total;
-    *rows = n > cap ? 0 : n;
+    SideLane *lane = nullptr;
+    const int rc = side_lane(pipeline, &lane);
+    if (rc != PMI_OK) return rc;
+    PMI_HIP(hipEventRecord(lane->stats_done[range], s));
+    if (range == 0) buf[1] = nullptr;
+    buf[range] = stats;
+    done[range] = lane->stats_done[range];
+    slot = pipeline ? SCR_LQ_STATS : SCR_STATS;
+    device = current_device();
+    bank = scratch_user_bank();
+    generation = scratch_generation_of(device, bank, slot);
+    return PMI_OK;
+}
+bool LastFitStats::valid() const { return buf[0] && generation == scratch_generation_of(device, bank, slot); }
+int LastFitStats::read(unsigned (&h)[16]) const
+{
+    for (unsigned &v : h) v = 0;
+    if (!valid()) return PMI_OK;      // no fit yet, or its buffers are gone
+    for (int k = 0; k < 2; k++) {
+        if (!buf[k]) continue;
+        unsigned part[16];
+        PMI_HIP(hipEventSynchronize(done[k]));
+        PMI_HIP(hipMemcpy(part, buf[k], 64, hipMemcpyDeviceToHost));
+        for (int i = 0; i < 16; i++) h[i] += part[i];
+    }
+    return PMI_OK;
 }
 
-int rows_to_fit(const int64_t *d_total, int64_t cap, const int64_t **d_rows, hipStream_t s)
+// ---- the fused calls' frame ranges -----------------------------------------------------------------------------
+// rows: [0] rows of A to fit, [1] rows of B to fit, [2] rows of A for the table, [3] rows of B for the table, [4] row offset of B.
+// A range whose candidates overflow its arrays (their columns were not written) fits none of them.
+__global__ void fit_rows_kernel(const int64_t *__restrict__ n_cand, int64_t capc, int64_t *__restrict__ rows_fit)
 {
-    void *ptr = nullptr;
-    int rc = scratch(SCR_ROWS, sizeof(int64_t), &ptr);
-    if (rc != PMI_OK) return rc;
-    hipLaunchKernelGGL(rows_to_fit_kernel, dim3(1), dim3(1), 0, s, d_total, cap, (int64_t *)ptr);
+    *rows_fit = *n_cand > capc ? 0 : *n_cand;
+}
+// The table rows once every count is known (cand_b == nullptr: one range; acc_* == nullptr: every candidate was kept).  A
+// range that overflowed its arrays: *d_out_n is the candidates' number, an upper bound of the rows; more rows than the
+// table holds: *d_out_n is theirs.  Either way no table row is written.
+__global__ void table_rows_kernel(const int64_t *__restrict__ cand_a, const unsigned *__restrict__ acc_a,
+                                  const int64_t *__restrict__ cand_b, const unsigned *__restrict__ acc_b, int64_t capc,
+                                  int64_t cap, int64_t *__restrict__ rows, int64_t *__restrict__ d_out_n)
+{
+    const int64_t ca = *cand_a, cb = cand_b ? *cand_b : 0;
+    const bool overflow = ca > capc || cb > capc;
+    const int64_t a = overflow ? 0 : (acc_a ? (int64_t)*acc_a : ca);
+    const int64_t b = overflow ? 0 : (acc_b ? (int64_t)*acc_b : cb);
+    const bool fits = !overflow && a + b <= cap;
+    rows[2] = fits ? a : 0;
+    rows[3] = fits ? b : 0;
+    rows[4] = a;
+    *d_out_n = overflow ? ca + cb : a + b;
+}
+
+// The scan is bound by memory requests, the fit by VALU issue: the scan of frame range B beside the fit of range A takes
+// less than the two one after the other.  A large call therefore cuts its frames in two: stream s runs
+// scan A, fit A; the side stream of the device's lane runs scan B (started when scan A is done) and fit B, with scratch from
+// the inner bank; the table is written once both counts are known (A's rows, then B's), so the capacity contract holds for
+// the sum.  A fit that keeps every candidate lets the last range fit its table rows, so that the counts need one kernel.
+int fused_ranges(const FusedRanges &c, int pipeline, int64_t F, int64_t Y, int64_t X, int64_t f_lo, int64_t f_hi,
+                 int64_t *d_out_n, hipStream_t s)
+{
+    const int64_t lo = f_lo < 0 ? 0 : f_lo, hi = f_hi > F - 1 ? F - 1 : f_hi, nf = hi - lo + 1;
+    // two ranges pay when each keeps the chip busy for a while (below ~1e8 pixels a range is a few tens of microseconds)
+    const bool two = g_localize_ranges == 2 && !g_kernel_timing && nf >= 16 && (double)nf * (double)Y * (double)X >= 2.5e8;
+    void *ptr = nullptr, *cptr = nullptr;
+    int rc;
+    // the counts of the ranges and the row bookkeeping live in the OUTER bank (both streams read them)
+    if ((rc = scratch(SCR_ROWS, 8 * sizeof(int64_t), &cptr)) != PMI_OK) return rc;
+    int64_t *n = (int64_t *)cptr, *rows = n + 2;              // n[r]: candidates of range r
+    if ((rc = scratch(SCR_IDS, c.ids_bytes, &ptr)) != PMI_OK) return rc;
+    void *ids[2] = {ptr, nullptr};
+    auto table_rows = [&](hipStream_t st) {
+        hipLaunchKernelGGL(table_rows_kernel, dim3(1), dim3(1), 0, st, (const int64_t *)n, c.rejects ? c.accepted(ids[0]) : nullptr,
+                           (const int64_t *)(two ? n + 1 : nullptr), c.rejects && two ? c.accepted(ids[1]) : nullptr, c.capc,
+                           c.cap, rows, d_out_n);
+    };
+    // the rows range r fits: its candidates, or, when the fit keeps every candidate, the last range its table rows
+    auto fit_rows = [&](int r, hipStream_t st) -> const int64_t * {
+        if (!c.rejects && r == (two ? 1 : 0)) {
+            table_rows(st);
+            return rows + 2 + r;
+        }
+        hipLaunchKernelGGL(fit_rows_kernel, dim3(1), dim3(1), 0, st, (const int64_t *)(n + r), c.capc, rows + r);
+        return rows + r;
+    };
+    if (!two) {
+        if ((rc = c.scan(ids[0], f_lo, f_hi, n, s)) != PMI_OK) return rc;
+        if ((rc = c.fit(ids[0], fit_rows(0, s), 0, s)) != PMI_OK) return rc;
+    } else {
+        SideLane *side_p = nullptr;
+        if ((rc = side_lane(pipeline, &side_p)) != PMI_OK) return rc;
+        SideLane &side = *side_p;
+        const int64_t mid = lo + nf / 2 - 1;                  // A = [lo, mid], B = [mid + 1, hi]
+        PMI_HIP(hipEventRecord(side.ev_start, s));           // the side stream joins the caller's stream order here
+        PMI_HIP(hipStreamWaitEvent(side.s2, side.ev_start, 0));
+        // From here on work may be queued on the side stream: whatever happens, the caller's stream is ordered after it
+        // before this call returns (a caller that frees or reuses its buffers on an error must not race kernels on s2).
+        struct Join {
+            SideLane &sd; hipStream_t st; bool done = false;
+            ~Join() { if (!done) { (void)hipEventRecord(sd.ev_b, sd.s2); (void)hipStreamWaitEvent(st, sd.ev_b, 0); } }
+        } join{side, s};
+        // ---- range A on the caller's stream
+        if ((rc = c.scan(ids[0], lo, mid, n, s)) != PMI_OK) return rc;
+        const int64_t *rows_a = fit_rows(0, s);
+        PMI_HIP(hipEventRecord(side.ev_scan_a, s));
+        if ((rc = c.fit(ids[0], rows_a, 0, s)) != PMI_OK) return rc;
+        // ---- range B on the side stream, scratch from the inner bank; its scan starts when scan A is done
+        PMI_HIP(hipStreamWaitEvent(side.s2, side.ev_scan_a, 0));
+        const int outer = scratch_enter_inner();
+        rc = scratch(SCR_IDS, c.ids_bytes, &ids[1]);
+        if (rc == PMI_OK) rc = c.scan(ids[1], mid + 1, hi, n + 1, side.s2);
+        if (rc == PMI_OK) rc = c.fit(ids[1], fit_rows(1, side.s2), 1, side.s2);
+        scratch_leave_inner(outer);
+        if (rc != PMI_OK) return rc;
+        PMI_HIP(hipEventRecord(side.ev_b, side.s2));
+        PMI_HIP(hipStreamWaitEvent(s, side.ev_b, 0));
+        join.done = true;
+    }
+    // ---- the table, once every count is known: A's rows, then B's
+    if (c.rejects) table_rows(s);
+    if ((rc = c.table(ids[0], rows + 2, nullptr, s)) != PMI_OK) return rc;
+    if (two && (rc = c.table(ids[1], rows + 3, rows + 4, s)) != PMI_OK) return rc;
     PMI_HIP(hipGetLastError());
-    *d_rows = (const int64_t *)ptr;
     return PMI_OK;
 }
 
@@ -175,7 +284,7 @@ void release_fft_plans();   // xcorr.hip
 
 extern "C" {
 
-int pmi_version(void) { return 107; }   // 0.1.7: + pmi_aim_* (AIM undrift); 0.1.6: round 6 (32-bit integer movies on the key scan, side lanes per (device, bank); + pmi_mle_set_libm / pmi_mle_get_libm / pmi_libm_eval_dev)
+int pmi_version(void) { return 108; }   // 0.1.8: - the pixel hand-off from the scan to the fit and its setter; 0.1.7: + pmi_aim_* (AIM undrift); 0.1.6: round 6 (32-bit integer movies on the key scan, side lanes per (device, bank); + pmi_mle_set_libm / pmi_mle_get_libm / pmi_libm_eval_dev)
 
 const char *pmi_last_error(void) { return pmi::g_err; }
 

@@ -310,11 +310,11 @@ def test_two_pipelines_in_flight_give_the_rows_of_one_pass():
     assert L.pmi_scratch_bank(2) != 0         # only banks 0 and 1 exist
 
 
-def test_fused_call_keeps_two_frame_ranges_in_flight():
+def test_fused_call_keeps_two_frame_ranges_in_flight_on_any_roi():
     """pmi_localize_mle_dev cuts a large frame range in two and runs the scan of the second half beside the fit of the
     first (its own side stream, the inner scratch bank): the table is the one of a single pass, bit for bit — whole
-    movie, a frame range with an odd number of frames, an ROI; the re-fit counts add up; a capacity below the sum of
-    the two halves reports the sum and leaves the table untouched."""
+    movie, a frame range with an odd number of frames, an ROI on an 8-pixel boundary and one off it; the re-fit counts
+    add up; a capacity below the sum of the two halves reports the sum and leaves the table untouched."""
     import torch
     from picasso_amd import _lib, backend, synth
     L = _lib.load()
@@ -339,7 +339,7 @@ def test_fused_call_keeps_two_frame_ranges_in_flight():
 
     try:
         n_full = 0
-        for f_lo, f_hi, roi in ((0, F - 1, None), (3, F - 5, None), (0, F - 1, (10, 20, 500, 490))):
+        for f_lo, f_hi, roi in ((0, F - 1, None), (3, F - 5, None), (0, F - 1, (10, 20, 500, 490)), (0, F - 1, (10, 21, 500, 490))):
             one, n1, refit1 = run(1, f_lo, f_hi, roi, cap)
             n_full = n_full or n1
             for rep in range(2):
@@ -347,23 +347,6 @@ def test_fused_call_keeps_two_frame_ranges_in_flight():
                 assert n1 == n2 and n1 > 20000, (n1, n2)
                 assert torch.equal(one[:, :n1], two[:, :n2]), (f_lo, f_hi, roi, rep)
                 assert refit1 == refit2 and refit1 > 0
-        # the pixel hand-off from the scan's exact stage to the fit (off by default): the same table, bit for bit
-        _lib.check(L.pmi_localize_set_handoff(1), "pmi_localize_set_handoff")
-        try:
-            hand = {}
-            for ranges in (1, 2):
-                hand[ranges] = run(ranges, 0, F - 1, None, cap)[:2]
-                assert hand[ranges][1] == n_full
-            hroi = run(1, 0, F - 1, (10, 21, 500, 490), cap)[:2]          # an ROI that starts off an 8-pixel boundary
-            _lib.check(L.pmi_localize_set_handoff(0), "pmi_localize_set_handoff")
-            for ranges in (1, 2):
-                plain, npl, _ = run(ranges, 0, F - 1, None, cap)
-                h, nh = hand[ranges]
-                assert npl == nh and torch.equal(plain[:, :npl], h[:, :nh]), ranges
-            plain, npl, _ = run(1, 0, F - 1, (10, 21, 500, 490), cap)
-            assert npl == hroi[1] and torch.equal(plain[:, :npl], hroi[0][:, :npl])
-        finally:
-            _lib.check(L.pmi_localize_set_handoff(0), "pmi_localize_set_handoff")
         # capacity between the first half's count and the total: nothing may be written; the count reported is the rows
         # needed — or, when even the candidates of the deferred exact stage overflow their scratch, their number (an upper bound)
         small, n_small, _ = run(2, 0, F - 1, None, int(n_full * 0.75), fill=0x5A5A5A5A)
