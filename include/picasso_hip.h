@@ -48,6 +48,9 @@
  *                      :206-250 _run_intersections_multithread, :275-320
  *                      _point_intersect_2d, :349-397 _point_intersect_3d): the
  *                      roi_cc counts of AIM undrift (:776-950 aim)
+ *   pmi_link_*, pmi_nena_*  picasso/postprocess.py:2441-2552 _get_link_groups,
+ *                      :2555-2661 _link_group_* as :2680-2821 _link_loc_groups
+ *                      uses them, :1212-1272 _nfndh / _fill_dnfl
  */
 #ifndef PICASSO_HIP_H
 #define PICASSO_HIP_H
@@ -468,6 +471,46 @@ int pmi_aim_roi_cc(int mode, const void *ref_x, const void *ref_y, const void *r
                    const void *y, const void *z, int64_t n, double rel_x, double rel_y, double rel_z,
                    double intersect_d, double width_units, double height_units, const void *shifts, int n_shifts,
                    int64_t *roi_cc);
+
+/* ---- link and NeNA (picasso/postprocess.py:2441-2661, :1212-1272, csrc/link.hip) ------------------------- *
+ * Device columns of a table SORTED BY FRAME: d_frame and d_group int64 (the host widens any integer column), d_x / d_y
+ * float32 or float64 (PMI_LINK_F32 / PMI_LINK_F64, each on its own).  At most 2^31 - 2 rows.  Scratch comes from the
+ * library's arena; every call runs on `stream`.
+ *
+ * pmi_link_frame_index_dev  d_lo[i] = first row j > i with frame[j] >= frame[i] + 1, d_hi[i] = first row j > i with
+ *                        frame[j] > frame[i] + k; n where there is none.
+ * pmi_link_groups_dev    the reference's int32 link_group of every row, group numbers in the order of their first row;
+ *                        r2 = d_max ** 2, k = max_dark_time + 1.  The last row of the table has no next row (the reference
+ *                        is undefined there).  *n_groups = the number of groups; synchronises the stream.
+ * pmi_link_combine_dev   per link group g < n_groups: d_count (uint32), d_first / d_last (min / max of d_frame, may be
+ *                        NULL with d_frame), d_last_row (the group's last row, -1 for an empty group), and per column
+ *                        descriptor a sum IN ROW ORDER in the column's own type:
+ *                          PMI_LINK_SUM    out[g] = sum data[i]                       out has data's type
+ *                          PMI_LINK_WSUM   out[g] = sum 1 / weight[i]^2                out has weight's type
+ *                          PMI_LINK_XWSUM  out[g] = sum data[i] * (1 / weight[i]^2)    float64 unless both are float32
+ *                        32-bit integers of either sign sum as PMI_LINK_U32 (the same bits), 64-bit ones as PMI_LINK_U64.
+ *                        Values of d_link_group outside [0, n_groups) are not summed.  At most 24 columns.
+ * pmi_nena_hist_dev      d_hist[n_bins] (uint64, device): next-frame neighbour distances d <= d_max of the same group,
+ *                        bin int(d / bin_size); rows i < 100 * int(n / 100) look forward, the last row of the table is
+ *                        never a neighbour and never looks forward, d / bin_size >= n_bins is dropped.  n_bins <= 8192. */
+enum pmi_link_type { PMI_LINK_F32 = 0, PMI_LINK_F64 = 1, PMI_LINK_U32 = 2, PMI_LINK_U64 = 3 };
+enum pmi_link_op { PMI_LINK_SUM = 0, PMI_LINK_WSUM = 1, PMI_LINK_XWSUM = 2 };
+typedef struct pmi_link_column {
+    const void *data;     /* device column (SUM, XWSUM) */
+    const void *weight;   /* device precision column lp (WSUM, XWSUM) */
+    void *out;            /* device, n_groups entries */
+    int32_t op, type, w_type;
+} pmi_link_column;
+int pmi_link_frame_index_dev(const int64_t *d_frame, int64_t n, int64_t k, int32_t *d_lo, int32_t *d_hi, void *stream);
+int pmi_link_groups_dev(const int64_t *d_frame, const void *d_x, int x_type, const void *d_y, int y_type,
+                        const int64_t *d_group, int64_t n, double r2, int64_t k, int32_t *d_link_group,
+                        int64_t *n_groups, void *stream);
+int pmi_link_combine_dev(const int32_t *d_link_group, int64_t n, int64_t n_groups, const int64_t *d_frame,
+                         const pmi_link_column *columns, int n_columns, uint32_t *d_count, int64_t *d_first,
+                         int64_t *d_last, int32_t *d_last_row, void *stream);
+int pmi_nena_hist_dev(const int64_t *d_frame, const void *d_x, int x_type, const void *d_y, int y_type,
+                      const int64_t *d_group, int64_t n, double d_max, double bin_size, int n_bins, uint64_t *d_hist,
+                      void *stream);
 
 /* ---- timing hooks for bench.py (HIP events on the given stream) ------- */
 int pmi_event_create(void **event);

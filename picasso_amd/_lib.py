@@ -111,6 +111,10 @@ SYMBOLS = {
     "pmi_aim_count_dev": (_i32, [_p, _p, _p, _p, _p, _i64, _f64, _f64, _f64, _p, _p]),
     "pmi_aim_table_destroy": (_i32, [_p]),
     "pmi_aim_roi_cc": (_i32, [_i32, _p, _p, _p, _i64, _p, _p, _p, _i64, _f64, _f64, _f64, _f64, _f64, _f64, _p, _i32, _p]),
+    "pmi_link_frame_index_dev": (_i32, [_p, _i64, _i64, _p, _p, _p]),
+    "pmi_link_groups_dev": (_i32, [_p, _p, _i32, _p, _i32, _p, _i64, _f64, _i64, _p, _p, _p]),
+    "pmi_link_combine_dev": (_i32, [_p, _i64, _i64, _p, _p, _i32, _p, _p, _p, _p, _p]),
+    "pmi_nena_hist_dev": (_i32, [_p, _p, _i32, _p, _i32, _p, _i64, _f64, _f64, _i32, _p, _p]),
     "pmi_event_create": (_i32, [_p]),
     "pmi_event_record": (_i32, [_p, _p]),
     "pmi_event_elapsed_ms": (_i32, [_p, _p, _p]),

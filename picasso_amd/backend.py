@@ -694,3 +694,143 @@ def aim_roi_cc_arrays(mode, ref, target, rel, intersect_d, width_units, height_u
                                               float(width_units), float(height_units), _lib.ptr(sh), int(sh.size),
                                               _lib.ptr(out)), "pmi_aim_roi_cc")
     return out
+
+
+# ---- link and NeNA (csrc/link.hip, picasso/postprocess.py:2441-2661, :1212-1272) ----
+LINK_F32, LINK_F64, LINK_U32, LINK_U64 = 0, 1, 2, 3
+LINK_SUM, LINK_WSUM, LINK_XWSUM = 0, 1, 2
+_LINK_TYPES = {np.dtype("float32"): LINK_F32, np.dtype("float64"): LINK_F64, np.dtype("uint32"): LINK_U32,
+               np.dtype("int32"): LINK_U32, np.dtype("uint64"): LINK_U64, np.dtype("int64"): LINK_U64}
+
+
+class _LinkColumn(ctypes.Structure):
+    _fields_ = [("data", ctypes.c_void_p), ("weight", ctypes.c_void_p), ("out", ctypes.c_void_p),
+                ("op", ctypes.c_int32), ("type", ctypes.c_int32), ("w_type", ctypes.c_int32)]
+
+
+def link_type(dtype, floating: bool = False) -> int:
+    dt = np.dtype(dtype)
+    if dt not in _LINK_TYPES or (floating and dt.kind != "f"):
+        raise TypeError(f"unsupported column dtype {dt} for link / NeNA on the device")
+    return _LINK_TYPES[dt]
+
+
+def _to_device(a, dtype=None):
+    """One host column -> a device tensor (integer columns widened on the host)."""
+    import torch
+    a = np.ascontiguousarray(a if dtype is None else np.asarray(a).astype(dtype, copy=False))
+    if a.dtype == np.uint32:
+        return torch.from_numpy(a.view(np.int32)).cuda()
+    if a.dtype == np.uint64:
+        return torch.from_numpy(a.view(np.int64)).cuda()
+    return torch.from_numpy(a).cuda()
+
+
+def _index_column(a, what: str):
+    a = np.asarray(a)
+    if a.dtype.kind not in "iub":
+        raise TypeError(f"{what} must be an integer column, not {a.dtype}")
+    return a.astype(np.int64, copy=False)
+
+
+class LinkTable:
+    """frame, x, y, group of a table sorted by frame, sent to the device once (frame / group widened to int64 on
+    the host; x / y stay float32 or float64, each on its own)."""
+
+    def __init__(self, frame, x, y, group):
+        import torch
+        _lib.require_gpu()
+        x, y = np.asarray(x), np.asarray(y)
+        self.n = int(len(x))
+        if not (len(frame) == len(y) == len(group) == self.n):
+            raise ValueError("frame, x, y and group must have one length")
+        self.x_type, self.y_type = link_type(x.dtype, True), link_type(y.dtype, True)
+        self.frame = _to_device(_index_column(frame, "frame"))
+        self.group = _to_device(_index_column(group, "group"))
+        self.x, self.y = _to_device(x), _to_device(y)
+        self.device = self.x.device
+        self.stream = torch.cuda.current_stream(self.device).cuda_stream
+
+    def frame_index(self, k: int):
+        """(lo, hi) int32 device tensors of pmi_link_frame_index_dev."""
+        import torch
+        lo = torch.empty(max(self.n, 1), dtype=torch.int32, device=self.device)
+        hi = torch.empty(max(self.n, 1), dtype=torch.int32, device=self.device)
+        with _lib.lock():
+            _lib.check(_lib.load().pmi_link_frame_index_dev(_dptr(self.frame), self.n, int(k), _dptr(lo), _dptr(hi),
+                                                            ctypes.c_void_p(self.stream)), "pmi_link_frame_index_dev")
+        return lo[:self.n], hi[:self.n]
+
+    def link_groups(self, r2: float, k: int):
+        """-> (int32 device tensor link_group, number of groups)."""
+        import torch
+        out = torch.empty(max(self.n, 1), dtype=torch.int32, device=self.device)
+        n_groups = ctypes.c_int64(0)
+        with _lib.lock():
+            _lib.check(_lib.load().pmi_link_groups_dev(
+                _dptr(self.frame), _dptr(self.x), self.x_type, _dptr(self.y), self.y_type, _dptr(self.group), self.n,
+                float(r2), int(k), _dptr(out), ctypes.byref(n_groups), ctypes.c_void_p(self.stream)),
+                "pmi_link_groups_dev")
+        return out[:self.n], int(n_groups.value)
+
+    def nena_hist(self, d_max: float, bin_size: float, n_bins: int) -> np.ndarray:
+        """int64 counts of the next-frame neighbour distance histogram."""
+        import torch
+        hist = torch.zeros(int(n_bins), dtype=torch.int64, device=self.device)
+        with _lib.lock():
+            _lib.check(_lib.load().pmi_nena_hist_dev(
+                _dptr(self.frame), _dptr(self.x), self.x_type, _dptr(self.y), self.y_type, _dptr(self.group), self.n,
+                float(d_max), float(bin_size), int(n_bins), _dptr(hist), ctypes.c_void_p(self.stream)),
+                "pmi_nena_hist_dev")
+            return hist.cpu().numpy()
+
+
+def link_combine(link_group, n_groups: int, frame, columns):
+    """Per link group: count, min / max frame, last row and the ordered sums of `columns`, a list of
+    (op, data, weight) with host columns (None where the op does not read one).
+    -> (uint32 count, int64 first, int64 last, int32 last_row, [sum arrays])."""
+    import torch
+    _lib.require_gpu()
+    n, G = int(len(link_group)), int(n_groups)
+    d_lg = link_group if isinstance(link_group, torch.Tensor) else _to_device(np.asarray(link_group, np.int32))
+    dev = d_lg.device
+    d_frame = None if frame is None else _to_device(_index_column(frame, "frame"))
+    cache, keep, outs = {}, [], []
+
+    def dev_col(a):
+        if a is None:
+            return None
+        if id(a) not in cache:
+            cache[id(a)] = _to_device(a)
+        return cache[id(a)]
+
+    desc = (_LinkColumn * max(len(columns), 1))()
+    for i, (op, data, weight) in enumerate(columns):
+        ta = link_type(data.dtype, op == LINK_XWSUM) if data is not None else 0
+        tw = link_type(weight.dtype, True) if weight is not None else 0
+        if op == LINK_SUM:
+            out_dt = data.dtype
+        elif op == LINK_WSUM:
+            out_dt = weight.dtype
+        else:
+            out_dt = np.promote_types(data.dtype, weight.dtype)
+        out = _to_device(np.zeros(max(G, 1), out_dt))
+        d, w = dev_col(data), dev_col(weight)
+        keep += [d, w]
+        outs.append((out, np.dtype(out_dt)))
+        desc[i] = _LinkColumn(d.data_ptr() if d is not None else None, w.data_ptr() if w is not None else None,
+                              out.data_ptr(), int(op), ta, tw)
+    count = torch.zeros(max(G, 1), dtype=torch.int32, device=dev)
+    first = torch.zeros(max(G, 1), dtype=torch.int64, device=dev)
+    last = torch.zeros(max(G, 1), dtype=torch.int64, device=dev)
+    last_row = torch.zeros(max(G, 1), dtype=torch.int32, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    with _lib.lock():
+        _lib.check(_lib.load().pmi_link_combine_dev(
+            _dptr(d_lg), n, G, _dptr(d_frame), ctypes.cast(desc, ctypes.c_void_p), len(columns), _dptr(count),
+            _dptr(first) if d_frame is not None else None, _dptr(last) if d_frame is not None else None,
+            _dptr(last_row), ctypes.c_void_p(stream)), "pmi_link_combine_dev")
+        sums = [o.cpu().numpy().view(dt)[:G] for o, dt in outs]
+        res = (count.cpu().numpy().view(np.uint32)[:G], first.cpu().numpy()[:G], last.cpu().numpy()[:G],
+               last_row.cpu().numpy()[:G])
+    return res + (sums,)

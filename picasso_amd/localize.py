@@ -783,6 +783,36 @@ def localize_file(path: str, camera_info: dict, parameters: dict, *, fitting_met
     return out
 
 
+MAX_LOCS = int(1e6)      # rows the quick checks look at (picasso/localize.py:50)
+
+
+def check_nena(locs: pd.DataFrame, info: None, callback: Callable[[int], None] = None) -> float:
+    """NeNA of (at most the first MAX_LOCS rows of) a table, in pixels; nan when it cannot be fitted
+    (picasso/localize.py:2037-2070)."""
+    from . import postprocess
+    print("Calculating NeNA.. ", end="")
+    locs = locs[0:MAX_LOCS]
+    try:
+        result, nena_px = postprocess.nena(locs, info, callback=callback)
+    except Exception as e:
+        print(e)
+        nena_px = float("nan")
+    print(f"{nena_px:.2f} px.")
+    return nena_px
+
+
+def check_kinetics(locs: pd.DataFrame, info: list[dict]) -> float:
+    """Mean length of the binding events of (at most the first MAX_LOCS rows of) a table, in frames
+    (picasso/localize.py:2073-2093)."""
+    from . import postprocess
+    print("Linking.. ", end="")
+    locs = locs.iloc[0:MAX_LOCS]
+    locs = postprocess.link(locs, info=info)
+    len_mean = locs.len.mean()
+    print(f"Mean length {len_mean:.2f} frames.")
+    return len_mean
+
+
 def _reference_module(given, name: str):
     if given is not None:
         return given
@@ -806,14 +836,17 @@ def install(picasso_localize=None, picasso_gaussmle=None, picasso_gausslq=None, 
     of once for `identify` and once for `get_spots`.  ``devices`` (see `set_devices`) then spreads the frame chunks over
     several GPUs of the process.  ``picasso_aim`` (default: ``picasso.aim`` when it imports) gets this package's AIM
     undrift (``aim``, ``intersection_max``, ``intersection_max_z``), which the Localize GUI, Render and
-    `picasso aim` call."""
+    `picasso aim` call.  ``picasso.postprocess`` also gets ``link``, ``nena`` and the functions under them
+    (``postprocess.LINK_NENA_NAMES``), and ``picasso.localize`` the two quick checks built on them, ``check_nena`` and
+    ``check_kinetics``."""
     if picasso_localize is None:
         import picasso.localize as picasso_localize       # the installed reference
     if picasso_gaussmle is None:
         import picasso.gaussmle as picasso_gaussmle
     import sys
     me = sys.modules[__name__]
-    for name in ("identify", "identify_by_frame_number", "identify_in_frame", "identify_in_image", "get_spots"):
+    for name in ("identify", "identify_by_frame_number", "identify_in_frame", "identify_in_image", "get_spots",
+                 "check_nena", "check_kinetics"):
         setattr(picasso_localize, name, getattr(me, name))
     picasso_localize._fit2d_gaussmle = _fit2d_gaussmle
     picasso_localize._fit2d_gausslq = _fit2d_gausslq
@@ -860,7 +893,7 @@ def install(picasso_localize=None, picasso_gaussmle=None, picasso_gausslq=None, 
     picasso_postprocess = _reference_module(picasso_postprocess, "postprocess")
     if picasso_postprocess is not None:
         from . import postprocess as amd_pp
-        for name in ("segment", "undrift"):
+        for name in ("segment", "undrift") + amd_pp.LINK_NENA_NAMES:
             setattr(picasso_postprocess, name, getattr(amd_pp, name))
     picasso_aim = _reference_module(picasso_aim, "aim")
     if picasso_aim is not None:

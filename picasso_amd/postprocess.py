@@ -1,17 +1,26 @@
 """The RCC drift-correction entry points of picasso.postprocess (picasso/postprocess.py:2824-2961
 ``n_segments``, ``segment``, ``undrift``; :3157-3218 ``_apply_drift`` / ``apply_drift``) on top of
-the GPU render (csrc/render.hip) and cross-correlation (csrc/xcorr.hip).
+the GPU render (csrc/render.hip) and cross-correlation (csrc/xcorr.hip), and linking and NeNA
+(:2007-2071 ``link``, :2422-2821 the link groups and their combination, :1058-1119 ``nena``, :1165-1239 the
+next-frame neighbour distance histogram) on top of csrc/link.hip.
 """
 from __future__ import annotations
 
+import math
 import warnings
+from collections import OrderedDict
+from typing import Callable, Literal
 
 import numpy as np
 import pandas as pd
 from scipy.interpolate import InterpolatedUnivariateSpline
+from scipy.optimize import curve_fit
 
 from . import backend, imageprocess, lib, render
 
+# what localize.install() rebinds on picasso.postprocess besides segment / undrift
+LINK_NENA_NAMES = ("link", "_get_link_groups", "get_link_groups", "_link_loc_groups", "link_loc_groups", "nena",
+                   "_next_frame_neighbor_distance_histogram", "next_frame_neighbor_distance_histogram")
 _SEGMENT_RENDER = {"blur_method": "gaussian", "min_blur_width": 1}      # what undrift renders its segments with
 
 
@@ -97,3 +106,246 @@ def undrift(locs: pd.DataFrame, info, segmentation: int, display: bool = True, s
     drift = pd.DataFrame({"x": _spline_over_frames(bounds, shift_x, n_frames),
                           "y": _spline_over_frames(bounds, shift_y, n_frames)})
     return drift, apply_drift(locs, info, drift=drift)
+
+
+# ---- link (postprocess.py:2007-2071, 2422-2821) -----------------------------------------------------------
+def _squared_like_numba(d_max) -> float:
+    """d_max ** 2 in the type numba gives d_max (a float32 stays float32, an integer stays an integer), as float64:
+    the jitted loops compare with it in float64."""
+    if isinstance(d_max, np.floating):
+        return float(d_max * d_max)
+    if isinstance(d_max, (int, np.integer)) and not isinstance(d_max, bool):
+        return float(int(d_max) * int(d_max))
+    return float(d_max) * float(d_max)
+
+
+def _device_link_groups(frame, x, y, d_max, max_dark_time, group):
+    table = backend.LinkTable(frame, x, y, group)
+    # frame > current + max_dark_time + 1 for integer frames: a fractional dark time counts as its floor
+    return table.link_groups(_squared_like_numba(d_max), math.floor(max_dark_time + 1))
+
+
+def _get_link_groups(frame, x, y, d_max: float, max_dark_time: int, group) -> np.ndarray:
+    """The int32 link group of every row of a table sorted by frame (postprocess.py:2441-2552): the reference's
+    greedy chains, group numbers in the order of their first row.  The last row of the table has no next row
+    (the reference is undefined there): its chain ends."""
+    if len(x) == 0:
+        return np.zeros(0, np.int32)
+    d_link_group, _ = _device_link_groups(frame, x, y, d_max, max_dark_time, group)
+    return d_link_group.cpu().numpy()
+
+
+def get_link_groups(frame, x, y, d_max: float, max_dark_time: int, group) -> np.ndarray:
+    """Alias to _get_link_groups, deprecated."""
+    lib.deprecation_warning("Deprecation warning: This function will become private in "
+                            "v0.11.0. Use _get_link_groups instead.")
+    return _get_link_groups(frame, x, y, d_max, max_dark_time, group)
+
+
+def _numba_mean(group_sum: np.ndarray, divisor: np.ndarray) -> np.ndarray:
+    """float32(group_sum / divisor) as the jitted _link_group_mean types it: integers join a float operand's
+    type (float32 / uint32 is a float32 division), two integer arrays divide in float64."""
+    a, b = group_sum.dtype, divisor.dtype
+    if a.kind in "iub" and b.kind in "iub":
+        dt = np.dtype(np.float64)
+    elif a.kind in "iub":
+        dt = b
+    elif b.kind in "iub":
+        dt = a
+    else:
+        dt = np.promote_types(a, b)
+    with np.errstate(all="ignore"):
+        return (group_sum.astype(dt) / divisor.astype(dt)).astype(np.float32)
+
+
+_LINK_MEANS = ("sx", "sy", "ellipticity", "net_gradient", "likelihood", "iterations", "d_zcalib")
+
+
+def _combine(locs: pd.DataFrame, info, link_group, n_groups: int, remove_ambiguous_lengths: bool) -> pd.DataFrame:
+    """_link_loc_groups with the group sums of every column in one pass on the device; `link_group` is a host array
+    or the device tensor the link groups were made in."""
+    has = locs.columns.__contains__
+    col = {c: locs[c].to_numpy() for c in locs.columns}
+    jobs, where = [], {}
+
+    def job(key, op, data, weight):
+        where[key] = len(jobs)
+        jobs.append((op, data, weight))
+
+    for axis, lp in (("x", "lpx"), ("y", "lpy")):
+        if has(axis):
+            job("w" + axis, backend.LINK_WSUM, None, col[lp])
+            job(axis, backend.LINK_XWSUM, col[axis], col[lp])
+    if has("z") and has("lpz"):
+        job("wz", backend.LINK_WSUM, None, col["lpz"])
+        job("z", backend.LINK_XWSUM, col["z"], col["lpz"])
+    elif has("z"):
+        job("z", backend.LINK_SUM, col["z"], None)
+    for c in ("photons", "bg") + _LINK_MEANS:
+        if has(c):
+            job(c, backend.LINK_SUM, col[c], None)
+    frame = col["frame"] if has("frame") else None
+    n_, first, last, last_row, sums = backend.link_combine(link_group, n_groups, frame, jobs)
+    empty = n_ == 0
+
+    def total(key):
+        return sums[where[key]]
+
+    columns = OrderedDict()
+    if has("frame"):
+        if empty.any():                      # the reference's start values of an empty group
+            first[empty], last[empty] = frame.max(), frame.min()
+        first_frame_, last_frame_ = first.astype(frame.dtype), last.astype(frame.dtype)
+        columns["frame"] = first_frame_
+    for axis in ("x", "y"):
+        if has(axis):
+            columns[axis] = _numba_mean(total(axis), total("w" + axis))
+    if has("photons"):
+        columns["photons"] = total("photons")
+    for c in ("sx", "sy"):
+        if has(c):
+            columns[c] = _numba_mean(total(c), n_)
+    if has("bg"):
+        columns["bg"] = total("bg")
+    with np.errstate(all="ignore"):
+        for axis in ("x", "y"):
+            if has(axis):
+                columns["lp" + axis] = np.sqrt(1 / total("w" + axis))
+        for c in ("ellipticity", "net_gradient", "likelihood", "iterations"):
+            if has(c):
+                columns[c] = _numba_mean(total(c), n_)
+        if has("z"):
+            if has("lpz"):
+                columns["z"] = _numba_mean(total("z"), total("wz"))
+                columns["lpz"] = np.sqrt(1 / total("wz"))
+            else:
+                columns["z"] = _numba_mean(total("z"), n_)
+        if has("d_zcalib"):
+            columns["d_zcalib"] = _numba_mean(total("d_zcalib"), n_)
+        if has("group"):
+            last_group = col["group"][np.where(empty, 0, last_row)]
+            if empty.any():
+                last_group[empty] = 0
+            columns["group"] = last_group
+        if has("frame"):
+            columns["len"] = last_frame_ - first_frame_ + 1
+        columns["n"] = n_
+        if has("photons"):
+            columns["photon_rate"] = np.float32(columns["photons"] / n_)
+    linked_locs = pd.DataFrame(columns)
+    if remove_ambiguous_lengths:
+        valid = np.logical_and(first_frame_ > 0, last_frame_ < info[0]["Frames"])
+        linked_locs = linked_locs[valid]
+    return linked_locs
+
+
+def _link_loc_groups(locs: pd.DataFrame, info, link_group, remove_ambiguous_lengths: bool = True) -> pd.DataFrame:
+    """Combine localizations into binding events (postprocess.py:2680-2821): per link group the first frame,
+    precision-weighted position, summed photons / background, mean shape columns, length and count."""
+    link_group = np.asarray(link_group)
+    if len(link_group) != len(locs):
+        raise ValueError("link_group must have one entry per localization")
+    if link_group.min() < 0:
+        raise ValueError("link_group must not be negative")
+    return _combine(locs, info, link_group.astype(np.int32, copy=False), int(link_group.max()) + 1,
+                    remove_ambiguous_lengths)
+
+
+def link_loc_groups(locs: pd.DataFrame, info, link_group, remove_ambiguous_lengths: bool = True) -> pd.DataFrame:
+    """Alias to _link_loc_groups, deprecated."""
+    lib.deprecation_warning("Deprecation warning: This function will become private in "
+                            "v0.11.0. Use _link_loc_groups instead.")
+    return _link_loc_groups(locs, info, link_group, remove_ambiguous_lengths)
+
+
+def link(locs: pd.DataFrame, info, r_max: float = 0.05, max_dark_time: int = 3,
+         combine_mode: Literal["average", "refit"] = "average", remove_ambiguous_lengths: bool = True) -> pd.DataFrame:
+    """Link localizations into binding events by their spatiotemporal proximity (postprocess.py:2007-2071).
+    The sort by frame is the reference's own pandas call on the host; everything behind it runs on the device."""
+    if len(locs) == 0:
+        linked_locs = locs.copy()
+        if "frame" in locs.columns:
+            linked_locs["len"] = np.array([], dtype=np.int32)
+            linked_locs["n"] = np.array([], dtype=np.int32)
+        if "photons" in locs.columns:
+            linked_locs["photon_rate"] = np.array([], dtype=np.float32)
+    else:
+        locs = locs.sort_values(kind="quicksort", by="frame")
+        if "group" in locs.columns:
+            group = locs["group"].to_numpy()
+        else:
+            group = np.zeros(len(locs), dtype=np.int32)
+        d_link_group, n_groups = _device_link_groups(locs["frame"].to_numpy(), locs["x"].to_numpy(),
+                                                     locs["y"].to_numpy(), r_max, max_dark_time, group)
+        if combine_mode == "average":
+            linked_locs = _combine(locs, info, d_link_group, n_groups, remove_ambiguous_lengths)
+        elif combine_mode == "refit":
+            raise NotImplementedError("Refit mode is not implemented yet. Please use 'average' mode.")
+    return linked_locs
+
+
+# ---- NeNA (postprocess.py:1058-1272) ------------------------------------------------------------------------
+def _nfndh(frame, x, y, group, d_max: float, bin_size: float, callback: Callable[[int], None] | None = None):
+    """Next-frame neighbour distance histogram of a table sorted by frame (postprocess.py:1212-1272), with the
+    reference's three quirks: the last len % 100 rows never look forward, the last row of the table is never a
+    neighbour, and a pair at exactly d_max (one past the last bin) is dropped.  The histogram is one kernel; the
+    callback then sees 1 .. 100."""
+    bins = np.arange(0, d_max, bin_size)
+    counts = backend.LinkTable(frame, x, y, group).nena_hist(d_max, bin_size, len(bins))
+    dnfl = counts.astype(np.float64)
+    if callback is not None:
+        for k in range(100):
+            callback(k + 1)
+    return bins + bin_size / 2, dnfl
+
+
+def _next_frame_neighbor_distance_histogram(locs: pd.DataFrame, callback: Callable[[int], None] | None = None):
+    """-> (bin_centers, dnfl).  Sorts ``locs`` by frame IN PLACE, as the reference does."""
+    locs.sort_values(kind="quicksort", by="frame", inplace=True)
+    frame = locs["frame"].to_numpy()
+    x = locs["x"].to_numpy()
+    y = locs["y"].to_numpy()
+    if "group" in locs.columns:
+        group = locs["group"].to_numpy()
+    else:
+        group = np.zeros(len(locs), dtype=np.int32)
+    return _nfndh(frame, x, y, group, 1.0, 0.001, callback)
+
+
+def next_frame_neighbor_distance_histogram(locs: pd.DataFrame, callback: Callable[[int], None] | None = None):
+    """Alias to _next_frame_neighbor_distance_histogram, deprecated."""
+    lib.deprecation_warning("Deprecation warning: This function will become private in "
+                            "v0.11.0. Use _next_frame_neighbor_distance_histogram instead.")
+    return _next_frame_neighbor_distance_histogram(locs, callback)
+
+
+def _nena_model(d, delta_a, s, ac, dc, sc):
+    a = ac + delta_a  # make sure a >= ac
+    p_single = a * (d / (2 * s**2)) * np.exp(-(d**2) / (4 * s**2))
+    p_short = ac / (sc * np.sqrt(2 * np.pi)) * np.exp(-0.5 * ((d - dc) / sc) ** 2)
+    return p_single + p_short
+
+
+def _nena_fit(bin_centers, dnfl, median_lp):
+    """The reference's curve_fit call on the histogram (postprocess.py:1097-1101), on the host."""
+    area = np.trapezoid(dnfl, bin_centers)
+    p0 = [0.8 * area, median_lp, 0.1 * area, 2 * median_lp, median_lp]
+    bounds = ([0, 0, 0, 0, 0], [np.inf, np.inf, np.inf, np.inf, np.inf])
+    popt, _ = curve_fit(_nena_model, bin_centers, dnfl, p0=p0, bounds=bounds)
+    return popt
+
+
+def nena(locs: pd.DataFrame, info=None, callback: Callable[[int], None] | None = None):
+    """NeNA, the experimental localization precision (postprocess.py:1058-1119) -> (result dict, s in pixels)."""
+    bin_centers, dnfl = _next_frame_neighbor_distance_histogram(locs, callback)
+    median_lp = np.mean([np.median(locs["lpx"]), np.median(locs["lpy"])])
+    popt = _nena_fit(bin_centers, dnfl, median_lp)
+    s = popt[1]
+    result = {
+        "d": bin_centers,
+        "data": dnfl,
+        "best_fit": _nena_model(bin_centers, *popt),
+        "best_values": {"delta_a": popt[0], "s": popt[1], "ac": popt[2], "dc": popt[3], "sc": popt[4]},
+        "pixelsize": lib.get_from_metadata(info, "Pixelsize", default="N/A"),
+    }
+    return result, s
