@@ -51,6 +51,8 @@
  *   pmi_link_*, pmi_nena_*  picasso/postprocess.py:2441-2552 _get_link_groups,
  *                      :2555-2661 _link_group_* as :2680-2821 _link_loc_groups
  *                      uses them, :1212-1272 _nfndh / _fill_dnfl
+ *   pmi_cluster_*      picasso/clusterer.py:114-201 _cluster (the SMLM clusterer),
+ *                      :34-111 _frame_analysis / frame_analysis, :410-445 _dbscan
  */
 #ifndef PICASSO_HIP_H
 #define PICASSO_HIP_H
@@ -511,6 +513,35 @@ int pmi_link_combine_dev(const int32_t *d_link_group, int64_t n, int64_t n_group
 int pmi_nena_hist_dev(const int64_t *d_frame, const void *d_x, int x_type, const void *d_y, int y_type,
                       const int64_t *d_group, int64_t n, double d_max, double bin_size, int n_bins, uint64_t *d_hist,
                       void *stream);
+
+/* ---- DBSCAN and the SMLM clusterer (picasso/clusterer.py:34-201, :410-445, csrc/cluster.hip) ------------------ *
+ * d_X: the points as float64, one column per dimension (dims * n values, dimension k at d_X + k * n), dims = 2 or 3, the
+ * third already scaled by radius_xy / radius_z.  lo / hi: host arrays of dims values that bound every column (rows outside
+ * are binned into the border cells: correct, slower).  r is the radius (it sizes the cells), r2 = r * r as the caller's
+ * float64 product: row j is a neighbour of row i, itself included, iff dx*dx + dy*dy (+ dz*dz) <= r2 in float64.  At most
+ * 2^31 - 2 rows; memory is O(n) whatever (hi - lo) / r is.  Scratch comes from the library's arena; every call runs on
+ * `stream` and the label calls synchronise it.
+ *
+ * pmi_cluster_counts_dev   d_counts[i] (int32) = the number of neighbours of row i.
+ * pmi_cluster_smlm_dev     d_labels[i] (int32) of _cluster: local maxima of the neighbour count (> min_locs), numbered in
+ *                          row order, merged and spread as the reference's loops do; labels of fewer than min_locs rows
+ *                          become -1; with d_frame (int64 per row, else NULL) the frame analysis below then runs on every
+ *                          label (fa_lo = 0.2 * n_frames, fa_hi = 0.8 * n_frames, fa_edges = the 21 bin edges, host).
+ * pmi_cluster_dbscan_dev   d_labels[i] (int32) of _dbscan: core rows have >= min_samples neighbours, clusters are numbered
+ *                          by their lowest core row, a border row takes the lowest number among its core neighbours,
+ *                          clusters of fewer than min_locs rows become -1 (the numbering keeps its gaps).
+ * pmi_cluster_frame_analysis_dev  d_pass[g] (int32) for the ids g < n_ids of d_ids (int32 per row, others ignored): 0 iff
+ *                          the mean of d_frame over the id's rows is < fa_lo or > fa_hi, or one of the 20 bins
+ *                          [fa_edges[k], fa_edges[k + 1]) (the last closed) holds more than 0.8 of its rows. */
+int pmi_cluster_counts_dev(const double *d_X, int dims, int64_t n, const double *lo, const double *hi, double r,
+                           double r2, int32_t *d_counts, void *stream);
+int pmi_cluster_smlm_dev(const double *d_X, int dims, int64_t n, const double *lo, const double *hi, double r,
+                         double r2, int64_t min_locs, const int64_t *d_frame, double fa_lo, double fa_hi,
+                         const double *fa_edges, int32_t *d_labels, void *stream);
+int pmi_cluster_dbscan_dev(const double *d_X, int dims, int64_t n, const double *lo, const double *hi, double r,
+                           double r2, int64_t min_samples, int64_t min_locs, int32_t *d_labels, void *stream);
+int pmi_cluster_frame_analysis_dev(const int32_t *d_ids, const int64_t *d_frame, int64_t n, int64_t n_ids, double fa_lo,
+                                   double fa_hi, const double *fa_edges, int32_t *d_pass, void *stream);
 
 /* ---- timing hooks for bench.py (HIP events on the given stream) ------- */
 int pmi_event_create(void **event);

@@ -834,3 +834,81 @@ def link_combine(link_group, n_groups: int, frame, columns):
         res = (count.cpu().numpy().view(np.uint32)[:G], first.cpu().numpy()[:G], last.cpu().numpy()[:G],
                last_row.cpu().numpy()[:G])
     return res + (sums,)
+
+
+# ---- DBSCAN and the SMLM clusterer (csrc/cluster.hip, picasso/clusterer.py:34-201, :410-445) ----
+class ClusterPoints:
+    """The points of a clustering call, sent to the device once: an (n, 2 | 3) array, widened to float64 as the
+    reference's KDTree and sklearn do, one column per dimension, with the corners the cells are counted from."""
+
+    def __init__(self, X):
+        import torch
+        _lib.require_gpu()
+        X = np.asarray(X)
+        if X.ndim != 2 or X.shape[1] not in (2, 3):
+            raise ValueError(f"points must have shape (n, 2) or (n, 3), not {X.shape}")
+        self.n, self.dims = int(X.shape[0]), int(X.shape[1])
+        cols = np.ascontiguousarray(X.T, np.float64)
+        if self.n:
+            self.lo, self.hi = np.ascontiguousarray(cols.min(axis=1)), np.ascontiguousarray(cols.max(axis=1))
+        else:
+            self.lo = self.hi = np.zeros(self.dims)
+        self.X = torch.from_numpy(cols).cuda()
+        self.device = self.X.device
+        self.stream = torch.cuda.current_stream(self.device).cuda_stream
+
+    def _out(self):
+        import torch
+        return torch.empty(max(self.n, 1), dtype=torch.int32, device=self.device)
+
+    def _head(self, radius):
+        r = float(radius)
+        return (_dptr(self.X), self.dims, self.n, _lib.ptr(self.lo), _lib.ptr(self.hi), r, r * r)
+
+    def counts(self, radius) -> np.ndarray:
+        """int32 neighbour count of every row (itself included)."""
+        out = self._out()
+        with _lib.lock():
+            _lib.check(_lib.load().pmi_cluster_counts_dev(*self._head(radius), _dptr(out), ctypes.c_void_p(self.stream)),
+                       "pmi_cluster_counts_dev")
+            return out[:self.n].cpu().numpy()
+
+    def smlm(self, radius, min_locs: int, frame=None, fa_lo=0.0, fa_hi=0.0, fa_edges=None) -> np.ndarray:
+        """int32 labels of the SMLM clusterer; `frame` (any integer column) adds the frame analysis."""
+        out = self._out()
+        d_frame = None if frame is None else _to_device(_index_column(frame, "frame"))
+        edges = None if fa_edges is None else np.ascontiguousarray(fa_edges, np.float64)
+        if d_frame is not None and (edges is None or edges.size != 21 or len(frame) != self.n):
+            raise ValueError("frame analysis needs one frame per row and 21 bin edges")
+        with _lib.lock():
+            _lib.check(_lib.load().pmi_cluster_smlm_dev(
+                *self._head(radius), int(min_locs), _dptr(d_frame), float(fa_lo), float(fa_hi), _lib.ptr(edges),
+                _dptr(out), ctypes.c_void_p(self.stream)), "pmi_cluster_smlm_dev")
+            return out[:self.n].cpu().numpy()
+
+    def dbscan(self, radius, min_samples: int, min_locs: int) -> np.ndarray:
+        """int32 DBSCAN labels, clusters of fewer than `min_locs` rows already -1."""
+        out = self._out()
+        with _lib.lock():
+            _lib.check(_lib.load().pmi_cluster_dbscan_dev(
+                *self._head(radius), int(min_samples), int(min_locs), _dptr(out), ctypes.c_void_p(self.stream)),
+                "pmi_cluster_dbscan_dev")
+            return out[:self.n].cpu().numpy()
+
+
+def cluster_frame_analysis(ids, frame, n_ids: int, fa_lo: float, fa_hi: float, fa_edges) -> np.ndarray:
+    """int32 pass flag of every id < n_ids (pmi_cluster_frame_analysis_dev); `ids` int32 per row, `frame` integers."""
+    import torch
+    _lib.require_gpu()
+    d_ids = _to_device(np.asarray(ids, np.int32))
+    d_frame = _to_device(_index_column(frame, "frame"))
+    edges = np.ascontiguousarray(fa_edges, np.float64)
+    if edges.size != 21 or len(ids) != len(frame):
+        raise ValueError("frame analysis needs one frame per row and 21 bin edges")
+    passed = torch.ones(max(int(n_ids), 1), dtype=torch.int32, device=d_ids.device)
+    stream = torch.cuda.current_stream(d_ids.device).cuda_stream
+    with _lib.lock():
+        _lib.check(_lib.load().pmi_cluster_frame_analysis_dev(
+            _dptr(d_ids), _dptr(d_frame), len(ids), int(n_ids), float(fa_lo), float(fa_hi), _lib.ptr(edges),
+            _dptr(passed), ctypes.c_void_p(stream)), "pmi_cluster_frame_analysis_dev")
+        return passed[:int(n_ids)].cpu().numpy()

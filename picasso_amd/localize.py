@@ -825,7 +825,7 @@ def _reference_module(given, name: str):
 
 def install(picasso_localize=None, picasso_gaussmle=None, picasso_gausslq=None, picasso_zfit=None,
             picasso_render=None, picasso_imageprocess=None, picasso_postprocess=None, *, fused: bool = False,
-            devices=None, picasso_aim=None) -> None:
+            devices=None, picasso_aim=None, picasso_clusterer=None) -> None:
     """Rebind the reference package's hot-path functions to this backend, so that
     picasso.__main__ and the GUI run on the GPU unchanged.  Modules not given are taken
     from the installed ``picasso`` package; the rows next to the path (z fit, render, RCC undrift) are rebound
@@ -838,7 +838,8 @@ def install(picasso_localize=None, picasso_gaussmle=None, picasso_gausslq=None, 
     undrift (``aim``, ``intersection_max``, ``intersection_max_z``), which the Localize GUI, Render and
     `picasso aim` call.  ``picasso.postprocess`` also gets ``link``, ``nena`` and the functions under them
     (``postprocess.LINK_NENA_NAMES``), and ``picasso.localize`` the two quick checks built on them, ``check_nena`` and
-    ``check_kinetics``."""
+    ``check_kinetics``.  ``picasso_clusterer`` (default: ``picasso.clusterer`` when it imports) gets DBSCAN, the SMLM
+    clusterer and the frame analysis (``clusterer.CLUSTERER_NAMES``); HDBSCAN and the cluster statistics stay its own."""
     if picasso_localize is None:
         import picasso.localize as picasso_localize       # the installed reference
     if picasso_gaussmle is None:
@@ -900,3 +901,8 @@ def install(picasso_localize=None, picasso_gaussmle=None, picasso_gausslq=None, 
         from . import aim as amd_aim
         for name in ("aim", "intersection_max", "intersection_max_z"):
             setattr(picasso_aim, name, getattr(amd_aim, name))
+    picasso_clusterer = _reference_module(picasso_clusterer, "clusterer")
+    if picasso_clusterer is not None:
+        from . import clusterer as amd_clusterer
+        for name in amd_clusterer.CLUSTERER_NAMES:
+            setattr(picasso_clusterer, name, getattr(amd_clusterer, name))
