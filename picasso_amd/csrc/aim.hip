@@ -25,40 +25,22 @@
 // sorted (rocPRIM radix sort) with counts by two bounded binary searches, and the target counters in an
 // open-addressing hash of 2x the segment's rows (bounded probe; no key value can be a sentinel, so a slot
 // holds 1 << 32 | key).  Every search and probe loop has a fixed bound and reports a status, never spins.
-#include <rocprim/device/device_radix_sort.hpp>
-
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
-#include "pmi_common.h"
+#include "rows_common.h"
 
 #pragma clang fp contract(off)
 
 namespace pmi {
 namespace aim {
 
-constexpr int BLOCK = 256;
+using rows::BLOCK;
+using rows::blocks;
+
 constexpr int MAX_SHIFTS = 8192;                   // roi_cc in LDS: 32 KB
 static int64_t g_dense_limit = int64_t(1) << 28;  // target-counter entries of the dense form (1 GiB)
-
-struct Table {
-    int mode = 0, nshift = 0, dense = 0;
-    double d = 0, W = 0, H = 0;
-    int32_t kmin = 0, kmax = 0;
-    uint32_t span = 0, tbase = 0, tsize = 0;      // dense: c_ref over [kmin, kmax], target counters over [kmin - S, kmax + S]
-    int32_t *cref = nullptr, *tcount = nullptr;
-    int32_t *sorted = nullptr;                     // sorted form: the n_ref keys, sorted
-    int64_t n_ref = 0;
-    unsigned long long *htab = nullptr;            // sorted form: target hash (1 << 32 | key, 0 = free)
-    int32_t *hcnt = nullptr;
-    uint64_t hsize = 0;
-    int32_t *shift_i = nullptr;                    // x / y shifts
-    double *shift_d = nullptr;                     // z shifts
-    int64_t *slots = nullptr;                      // per target row: its counter slot, -1 = none
-    int64_t slots_cap = 0;
-    int device = 0;
-};
 
 struct Cols {
     const void *x, *y, *z;
@@ -140,21 +122,28 @@ __device__ __forceinline__ uint32_t hash32(uint32_t k)
     return k;
 }
 
+// what the kernels read of a table, passed by value; the arrays stay the table's from create to destroy
 struct Dev {
-    int nshift, dense;
-    double d, W, H;
-    int32_t kmin;
-    uint32_t span, tbase, tsize;
-    const int32_t *cref;
-    int32_t *tcount;
-    const int32_t *sorted;
-    int64_t n_ref;
-    unsigned long long *htab;
-    int32_t *hcnt;
-    uint64_t hsize;
-    const int32_t *shift_i;
-    const double *shift_d;
-    int64_t *slots;
+    int nshift = 0, dense = 0;
+    double d = 0, W = 0, H = 0;
+    int32_t kmin = 0;
+    uint32_t span = 0, tbase = 0, tsize = 0;      // dense: c_ref over [kmin, kmax], target counters over [kmin - S, kmax + S]
+    int32_t *cref = nullptr, *tcount = nullptr;
+    int32_t *sorted = nullptr;                     // sorted form: the n_ref keys, sorted
+    int64_t n_ref = 0;
+    unsigned long long *htab = nullptr;            // sorted form: target hash (1 << 32 | key, 0 = free)
+    int32_t *hcnt = nullptr;
+    uint64_t hsize = 0;
+    int32_t *shift_i = nullptr;                    // x / y shifts
+    double *shift_d = nullptr;                     // z shifts
+    int64_t *slots = nullptr;                      // per target row: its counter slot, -1 = none
+};
+
+struct Table {
+    Dev v;
+    int mode = 0, device = 0;
+    int32_t kmax = 0;
+    int64_t slots_cap = 0;
 };
 
 __device__ __forceinline__ int32_t ref_count(const Dev &t, int32_t q)
@@ -260,17 +249,17 @@ __global__ void seg_scatter_kernel(const int64_t *__restrict__ frame, int64_t n,
     if (f >= 1 && f <= n_frames) rows[atomicAdd((unsigned long long *)&cursor[(f - 1) / seg_len], 1ull)] = (int32_t)i;
 }
 
-static Dev dev_view(const Table &t)
-{
-    Dev v;
-    v.nshift = t.nshift; v.dense = t.dense; v.d = t.d; v.W = t.W; v.H = t.H; v.kmin = t.kmin;
-    v.span = t.span; v.tbase = t.tbase; v.tsize = t.tsize; v.cref = t.cref; v.tcount = t.tcount;
-    v.sorted = t.sorted; v.n_ref = t.n_ref; v.htab = t.htab; v.hcnt = t.hcnt; v.hsize = t.hsize;
-    v.shift_i = t.shift_i; v.shift_d = t.shift_d; v.slots = t.slots;
-    return v;
-}
-
-static unsigned blocks(int64_t n, int b = BLOCK) { return (unsigned)((n + b - 1) / b); }
+// kernel<MODE> of the table's key arithmetic
+#define PMI_AIM_DISPATCH(mode, kernel, grid, lds, stream, ...)                                               \
+    do {                                                                                                     \
+        switch (mode) {                                                                                      \
+        case PMI_AIM_XY_F32: kernel<PMI_AIM_XY_F32><<<grid, BLOCK, lds, stream>>>(__VA_ARGS__); break;       \
+        case PMI_AIM_XY_F64: kernel<PMI_AIM_XY_F64><<<grid, BLOCK, lds, stream>>>(__VA_ARGS__); break;       \
+        case PMI_AIM_Z_F32: kernel<PMI_AIM_Z_F32><<<grid, BLOCK, lds, stream>>>(__VA_ARGS__); break;         \
+        default: kernel<PMI_AIM_Z_F64><<<grid, BLOCK, lds, stream>>>(__VA_ARGS__); break;                    \
+        }                                                                                                    \
+        PMI_HIP(hipGetLastError());                                                                          \
+    } while (0)
 
 static void release(Table *t)
 {
@@ -278,8 +267,9 @@ static void release(Table *t)
     int cur = 0;
     (void)hipGetDevice(&cur);
     (void)hipSetDevice(t->device);
-    for (void *p : {(void *)t->cref, (void *)t->tcount, (void *)t->sorted, (void *)t->htab, (void *)t->hcnt,
-                    (void *)t->shift_i, (void *)t->shift_d, (void *)t->slots})
+    const Dev &v = t->v;
+    for (void *p : {(void *)v.cref, (void *)v.tcount, (void *)v.sorted, (void *)v.htab, (void *)v.hcnt,
+                    (void *)v.shift_i, (void *)v.shift_d, (void *)v.slots})
         if (p) (void)hipFree(p);
     (void)hipSetDevice(cur);
     delete t;
@@ -306,66 +296,50 @@ static int table_create(int mode, Cols ref, double d, double W, double H, const 
         return PMI_ERR_ARG;
     }
     Table *t = new Table;
-    t->mode = mode; t->nshift = nshift; t->d = d; t->W = W; t->H = H; t->n_ref = ref.n;
+    Dev &v = t->v;
+    t->mode = mode; v.nshift = nshift; v.d = d; v.W = W; v.H = H; v.n_ref = ref.n;
     (void)hipGetDevice(&t->device);
     struct Guard { Table *&t; ~Guard() { release(t); } } guard{t};
     const bool xy = mode < PMI_AIM_Z_F32;
     int64_t max_shift = 0;
     if (xy) {
-        PMI_HIP(hipMalloc(&t->shift_i, sizeof(int32_t) * nshift));
-        PMI_HIP(hipMemcpyAsync(t->shift_i, shifts, sizeof(int32_t) * nshift, hipMemcpyHostToDevice, s));
+        PMI_HIP(hipMalloc(&v.shift_i, sizeof(int32_t) * nshift));
+        PMI_HIP(hipMemcpyAsync(v.shift_i, shifts, sizeof(int32_t) * nshift, hipMemcpyHostToDevice, s));
         for (int i = 0; i < nshift; ++i) max_shift = std::max<int64_t>(max_shift, std::llabs((long long)((const int32_t *)shifts)[i]));
     } else {
-        PMI_HIP(hipMalloc(&t->shift_d, sizeof(double) * nshift));
-        PMI_HIP(hipMemcpyAsync(t->shift_d, shifts, sizeof(double) * nshift, hipMemcpyHostToDevice, s));
+        PMI_HIP(hipMalloc(&v.shift_d, sizeof(double) * nshift));
+        PMI_HIP(hipMemcpyAsync(v.shift_d, shifts, sizeof(double) * nshift, hipMemcpyHostToDevice, s));
     }
-    int32_t *keys = nullptr, *mm = nullptr;
-    struct Tmp { int32_t *&k, *&m; ~Tmp() { if (k) (void)hipFree(k); if (m) (void)hipFree(m); } } tmp{keys, mm};
-    PMI_HIP(hipMalloc(&keys, sizeof(int32_t) * std::max<int64_t>(ref.n, 1)));
-    PMI_HIP(hipMalloc(&mm, sizeof(int32_t) * 2));
+    // the reference keys and their min / max die with this call (the stream is synchronised before it returns)
+    int32_t *keys, *mm;
+    rc = rows::carve(SCR_STAGE_A, [&](rows::Arena &ar) {
+        keys = ar.take<int32_t>(std::max<int64_t>(ref.n, 1));
+        mm = ar.take<int32_t>(2);
+    });
+    if (rc != PMI_OK) return rc;
     const int32_t init[2] = {INT32_MAX, INT32_MIN};
     PMI_HIP(hipMemcpyAsync(mm, init, sizeof(init), hipMemcpyHostToDevice, s));
-    if (ref.n > 0) {
-        switch (mode) {
-        case PMI_AIM_XY_F32: ref_keys_kernel<PMI_AIM_XY_F32><<<blocks(ref.n), BLOCK, 0, s>>>(ref, d, W, H, keys, mm); break;
-        case PMI_AIM_XY_F64: ref_keys_kernel<PMI_AIM_XY_F64><<<blocks(ref.n), BLOCK, 0, s>>>(ref, d, W, H, keys, mm); break;
-        case PMI_AIM_Z_F32: ref_keys_kernel<PMI_AIM_Z_F32><<<blocks(ref.n), BLOCK, 0, s>>>(ref, d, W, H, keys, mm); break;
-        default: ref_keys_kernel<PMI_AIM_Z_F64><<<blocks(ref.n), BLOCK, 0, s>>>(ref, d, W, H, keys, mm); break;
-        }
-        PMI_HIP(hipGetLastError());
-    }
+    if (ref.n > 0) PMI_AIM_DISPATCH(mode, ref_keys_kernel, blocks(ref.n), 0, s, ref, d, W, H, keys, mm);
     int32_t hmm[2];
     PMI_HIP(hipMemcpyAsync(hmm, mm, sizeof(hmm), hipMemcpyDeviceToHost, s));
     PMI_HIP(hipStreamSynchronize(s));
     if (ref.n == 0) { hmm[0] = 0; hmm[1] = -1; }
-    t->kmin = hmm[0]; t->kmax = hmm[1];
+    v.kmin = hmm[0]; t->kmax = hmm[1];
     const int64_t span = (int64_t)hmm[1] - hmm[0] + 1;          // 0 for an empty reference
     const int64_t tsize = span + 2 * max_shift;
     if (xy && tsize <= g_dense_limit) {
-        t->dense = 1;
-        t->span = (uint32_t)span;
-        t->tsize = (uint32_t)tsize;
-        t->tbase = (uint32_t)((int64_t)t->kmin - max_shift);
-        PMI_HIP(hipMalloc(&t->cref, sizeof(int32_t) * std::max<int64_t>(span, 1)));
-        PMI_HIP(hipMalloc(&t->tcount, sizeof(int32_t) * std::max<int64_t>(tsize, 1)));
-        PMI_HIP(hipMemsetAsync(t->cref, 0, sizeof(int32_t) * std::max<int64_t>(span, 1), s));
-        PMI_HIP(hipMemsetAsync(t->tcount, 0, sizeof(int32_t) * std::max<int64_t>(tsize, 1), s));
-        if (ref.n > 0) {
-            dense_add_kernel<<<blocks(ref.n), BLOCK, 0, s>>>(keys, ref.n, t->kmin, t->cref);
-            PMI_HIP(hipGetLastError());
-        }
+        v.dense = 1;
+        v.span = (uint32_t)span;
+        v.tsize = (uint32_t)tsize;
+        v.tbase = (uint32_t)((int64_t)v.kmin - max_shift);
+        PMI_HIP(hipMalloc(&v.cref, sizeof(int32_t) * std::max<int64_t>(span, 1)));
+        PMI_HIP(hipMalloc(&v.tcount, sizeof(int32_t) * std::max<int64_t>(tsize, 1)));
+        PMI_HIP(hipMemsetAsync(v.cref, 0, sizeof(int32_t) * std::max<int64_t>(span, 1), s));
+        PMI_HIP(hipMemsetAsync(v.tcount, 0, sizeof(int32_t) * std::max<int64_t>(tsize, 1), s));
+        if (ref.n > 0) PMI_LAUNCH(dense_add_kernel, ref.n, s, keys, ref.n, v.kmin, v.cref);
     } else {
-        PMI_HIP(hipMalloc(&t->sorted, sizeof(int32_t) * std::max<int64_t>(ref.n, 1)));
-        if (ref.n > 0) {
-            size_t bytes = 0;
-            PMI_HIP(rocprim::radix_sort_keys(nullptr, bytes, keys, t->sorted, (size_t)ref.n, 0, 32, s));
-            void *work = nullptr;
-            PMI_HIP(hipMalloc(&work, std::max<size_t>(bytes, 1)));
-            hipError_t e = rocprim::radix_sort_keys(work, bytes, keys, t->sorted, (size_t)ref.n, 0, 32, s);
-            if (e == hipSuccess) e = hipStreamSynchronize(s);
-            (void)hipFree(work);
-            PMI_HIP(e);
-        }
+        PMI_HIP(hipMalloc(&v.sorted, sizeof(int32_t) * std::max<int64_t>(ref.n, 1)));
+        if (ref.n > 0 && (rc = rows::sort_keys(keys, v.sorted, (size_t)ref.n, 32, s)) != PMI_OK) return rc;
     }
     PMI_HIP(hipStreamSynchronize(s));
     *out = t;
@@ -379,39 +353,31 @@ static int count(Table *t, Cols c, double rx, double ry, double rz, int32_t *d_o
         set_error("pmi_aim_count_dev: no table, no output or %lld rows", (long long)c.n);
         return PMI_ERR_ARG;
     }
+    Dev &v = t->v;
     if (c.n > t->slots_cap) {
         PMI_HIP(hipStreamSynchronize(s));
-        if (t->slots) { (void)hipFree(t->slots); t->slots = nullptr; t->slots_cap = 0; }
-        PMI_HIP(hipMalloc(&t->slots, sizeof(int64_t) * c.n));
+        if (v.slots) { (void)hipFree(v.slots); v.slots = nullptr; t->slots_cap = 0; }
+        PMI_HIP(hipMalloc(&v.slots, sizeof(int64_t) * c.n));
         t->slots_cap = c.n;
     }
-    if (!t->dense && 2 * (uint64_t)c.n > t->hsize) {
+    if (!v.dense && 2 * (uint64_t)c.n > v.hsize) {
         uint64_t h = 1024;
         while (h < 2 * (uint64_t)c.n) h <<= 1;
         PMI_HIP(hipStreamSynchronize(s));
-        if (t->htab) { (void)hipFree(t->htab); t->htab = nullptr; }
-        if (t->hcnt) { (void)hipFree(t->hcnt); t->hcnt = nullptr; }
-        t->hsize = 0;
-        PMI_HIP(hipMalloc(&t->htab, sizeof(unsigned long long) * h));
-        PMI_HIP(hipMalloc(&t->hcnt, sizeof(int32_t) * h));
-        PMI_HIP(hipMemsetAsync(t->htab, 0, sizeof(unsigned long long) * h, s));
-        PMI_HIP(hipMemsetAsync(t->hcnt, 0, sizeof(int32_t) * h, s));
-        t->hsize = h;
+        if (v.htab) { (void)hipFree(v.htab); v.htab = nullptr; }
+        if (v.hcnt) { (void)hipFree(v.hcnt); v.hcnt = nullptr; }
+        v.hsize = 0;
+        PMI_HIP(hipMalloc(&v.htab, sizeof(unsigned long long) * h));
+        PMI_HIP(hipMalloc(&v.hcnt, sizeof(int32_t) * h));
+        PMI_HIP(hipMemsetAsync(v.htab, 0, sizeof(unsigned long long) * h, s));
+        PMI_HIP(hipMemsetAsync(v.hcnt, 0, sizeof(int32_t) * h, s));
+        v.hsize = h;
     }
-    PMI_HIP(hipMemsetAsync(d_out, 0, sizeof(int32_t) * (t->nshift + 1), s));
+    PMI_HIP(hipMemsetAsync(d_out, 0, sizeof(int32_t) * (v.nshift + 1), s));
     if (c.n == 0) return PMI_OK;
-    const Dev v = dev_view(*t);
     const unsigned grid = (unsigned)std::min<int64_t>(blocks(c.n), 8 * (int64_t)device_cu_count());
-    const size_t lds = sizeof(int32_t) * t->nshift;
-    switch (t->mode) {
-    case PMI_AIM_XY_F32: count_kernel<PMI_AIM_XY_F32><<<grid, BLOCK, lds, s>>>(v, c, rx, ry, rz, d_out); break;
-    case PMI_AIM_XY_F64: count_kernel<PMI_AIM_XY_F64><<<grid, BLOCK, lds, s>>>(v, c, rx, ry, rz, d_out); break;
-    case PMI_AIM_Z_F32: count_kernel<PMI_AIM_Z_F32><<<grid, BLOCK, lds, s>>>(v, c, rx, ry, rz, d_out); break;
-    default: count_kernel<PMI_AIM_Z_F64><<<grid, BLOCK, lds, s>>>(v, c, rx, ry, rz, d_out); break;
-    }
-    PMI_HIP(hipGetLastError());
-    cleanup_kernel<<<blocks(c.n), BLOCK, 0, s>>>(v, c.n);
-    PMI_HIP(hipGetLastError());
+    PMI_AIM_DISPATCH(t->mode, count_kernel, grid, sizeof(int32_t) * v.nshift, s, v, c, rx, ry, rz, d_out);
+    PMI_LAUNCH(cleanup_kernel, c.n, s, v, c.n);
     return PMI_OK;
 }
 
@@ -444,25 +410,22 @@ int pmi_aim_partition_dev(const int64_t *d_frame, int64_t n, int64_t seg_len, in
     const int64_t n_seg = (n_frames + seg_len - 1) / seg_len;
     seg_offsets[0] = 0;
     if (n_seg == 0) return PMI_OK;
-    int32_t *counts = nullptr;
-    int64_t *cursor = nullptr;
-    struct Tmp { int32_t *&a; int64_t *&b; ~Tmp() { if (a) (void)hipFree(a); if (b) (void)hipFree(b); } } tmp{counts, cursor};
-    PMI_HIP(hipMalloc(&counts, sizeof(int32_t) * n_seg));
-    PMI_HIP(hipMalloc(&cursor, sizeof(int64_t) * n_seg));
+    // counts and cursor die with this call (the stream is synchronised before it returns)
+    int32_t *counts;
+    int64_t *cursor;
+    const int rc = rows::carve(SCR_STAGE_A, [&](rows::Arena &ar) {
+        counts = ar.take<int32_t>(n_seg);
+        cursor = ar.take<int64_t>(n_seg);
+    });
+    if (rc != PMI_OK) return rc;
     PMI_HIP(hipMemsetAsync(counts, 0, sizeof(int32_t) * n_seg, s));
-    if (n > 0) {
-        aim::seg_hist_kernel<<<aim::blocks(n), aim::BLOCK, 0, s>>>(d_frame, n, seg_len, n_frames, counts);
-        PMI_HIP(hipGetLastError());
-    }
+    if (n > 0) PMI_LAUNCH(aim::seg_hist_kernel, n, s, d_frame, n, seg_len, n_frames, counts);
     std::vector<int32_t> h(n_seg);
     PMI_HIP(hipMemcpyAsync(h.data(), counts, sizeof(int32_t) * n_seg, hipMemcpyDeviceToHost, s));
     PMI_HIP(hipStreamSynchronize(s));
     for (int64_t i = 0; i < n_seg; ++i) seg_offsets[i + 1] = seg_offsets[i] + h[i];
     PMI_HIP(hipMemcpyAsync(cursor, seg_offsets, sizeof(int64_t) * n_seg, hipMemcpyHostToDevice, s));
-    if (n > 0) {
-        aim::seg_scatter_kernel<<<aim::blocks(n), aim::BLOCK, 0, s>>>(d_frame, n, seg_len, n_frames, cursor, d_rows);
-        PMI_HIP(hipGetLastError());
-    }
+    if (n > 0) PMI_LAUNCH(aim::seg_scatter_kernel, n, s, d_frame, n, seg_len, n_frames, cursor, d_rows);
     PMI_HIP(hipStreamSynchronize(s));
     return PMI_OK;
 }
@@ -489,8 +452,8 @@ int pmi_aim_table_info(void *table, int *dense, int64_t *entries)
         set_error("pmi_aim_table_info: table == NULL");
         return PMI_ERR_ARG;
     }
-    if (dense) *dense = t->dense;
-    if (entries) *entries = t->dense ? (int64_t)t->span : t->n_ref;
+    if (dense) *dense = t->v.dense;
+    if (entries) *entries = t->v.dense ? (int64_t)t->v.span : t->v.n_ref;
     return PMI_OK;
 }
 

@@ -28,23 +28,19 @@
 // Then labels with fewer than min_locs rows become -1 (integer atomics: the order does not matter), and with a frame
 // column every label is checked by its mean frame and its fullest of 20 time bins.  No float atomics or reductions.
 // Every loop is bounded by the row count; a union or a chain that does not settle reports a status.
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-
 #include <algorithm>
 
-#include "pmi_common.h"
+#include "rows_common.h"
 
 #pragma clang fp contract(off)
 
 namespace pmi {
 namespace cluster {
 
-constexpr int BLOCK = 256;
+using namespace rows;
+
 constexpr int FA_BINS = 20;
 constexpr int MAX_ROUNDS = 40;       // pointer jumping doubles the distance covered: 31 rounds for 2^31 rows
-
-static inline unsigned blocks(int64_t n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
 
 struct Grid {
     double lo[3];
@@ -85,17 +81,6 @@ __global__ void key_kernel(const double *__restrict__ X, int32_t n, Grid g, uint
     rows[i] = (int32_t)i;
 }
 
-// first position in [0, n) of the sorted keys that is >= v
-__device__ __forceinline__ int32_t key_lower_bound(const uint64_t *__restrict__ keys, int32_t n, uint64_t v)
-{
-    int32_t lo = 0, hi = n;
-    for (int it = 0; it < 40 && lo < hi; ++it) {
-        const int32_t mid = lo + ((hi - lo) >> 1);
-        if (keys[mid] < v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 template <int D>
 __global__ void gather_kernel(const double *__restrict__ X, const uint64_t *__restrict__ keys,
                               const int32_t *__restrict__ rows, int32_t n, Grid g, double *__restrict__ xs,
@@ -125,8 +110,8 @@ __global__ void gather_kernel(const double *__restrict__ X, const uint64_t *__re
             if (cx >= 0 && cx <= g.maxc[0] && (D == 2 || (cy >= 0 && cy <= g.maxc[1]))) {
                 uint64_t base = (uint64_t)cx << g.shift[0];
                 if (D == 3) base |= (uint64_t)cy << g.shift[1];
-                a = key_lower_bound(keys, n, base | (uint64_t)l0);
-                b = key_lower_bound(keys, n, (base | (uint64_t)l1) + 1u);
+                a = lower_bound(keys, 0, n, base | (uint64_t)l0);
+                b = lower_bound(keys, 0, n, (base | (uint64_t)l1) + 1u);
             }
             rlo[(size_t)k * n + p] = a;
             rhi[(size_t)k * n + p] = b;
@@ -233,36 +218,6 @@ __global__ void jump_kernel(int32_t *lab, int32_t n, int32_t *pending)
 }
 
 // ---- DBSCAN ------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int32_t find_root(const int32_t *parent, int32_t v, int32_t n)
-{
-    // a parent is always a lower row: at most n steps
-    for (int32_t it = 0; it < n; ++it) {
-        const int32_t p = __hip_atomic_load(parent + v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (p == v) return v;
-        v = p;
-    }
-    return v;
-}
-
-// status[0] is set when a union did not settle
-__device__ __forceinline__ void unite(int32_t *parent, int32_t a, int32_t b, int32_t n, int32_t *status)
-{
-    for (int32_t it = 0; it < n; ++it) {
-        a = find_root(parent, a, n);
-        b = find_root(parent, b, n);
-        if (a == b) return;
-        const int32_t low = min(a, b), high = max(a, b);
-        if (atomicCAS(parent + high, high, low) == high) return;
-    }
-    atomicExch(status, 1);
-}
-
-__global__ void iota_kernel(int32_t *a, int32_t n)
-{
-    const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (i < n) a[i] = (int32_t)i;
-}
-
 // parent[] is indexed by the caller's rows
 template <int D>
 __global__ void union_kernel(Tab t, const int32_t *__restrict__ cnt, int64_t min_samples, int32_t *parent,
@@ -381,19 +336,6 @@ __global__ void scatter_kernel(const int32_t *__restrict__ lab, const int32_t *_
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------
-// one scratch slot cut into 256-byte aligned pieces; a first pass without a base only measures
-struct Arena {
-    char *base = nullptr;
-    size_t used = 0;
-    template <typename T>
-    T *take(size_t count)
-    {
-        T *p = base ? (T *)(base + used) : nullptr;
-        used += (count * sizeof(T) + 255) & ~size_t(255);
-        return p;
-    }
-};
-
 static int check_args(const char *what, const double *d_X, int dims, int64_t n, const double *lo, const double *hi,
                       double r, double r2)
 {
@@ -468,48 +410,21 @@ static void layout(Arena &ar, Work &w, int dims, size_t N)
     w.status = ar.take<int32_t>(4);
 }
 
-#define PMI_LAUNCH(kernel, count, ...)                             \
-    do {                                                           \
-        kernel<<<blocks(count), BLOCK, 0, s>>>(__VA_ARGS__);       \
-        PMI_HIP(hipGetLastError());                                \
-    } while (0)
-
 // cell sort, candidate ranges and neighbour counts: everything both algorithms start from
 template <int D>
 static int prepare(const double *d_X, int32_t n, const double *lo, const double *hi, double r, double r2, Work &w,
                    Tab &t, hipStream_t s)
 {
     const size_t N = (size_t)n;
-    Arena measure;
-    layout(measure, w, D, N);
-    void *base = nullptr;
-    int rc = scratch(SCR_STAGE_A, measure.used, &base);
+    int rc = carve(SCR_STAGE_A, [&](Arena &ar) { layout(ar, w, D, N); });
     if (rc != PMI_OK) return rc;
-    Arena ar;
-    ar.base = (char *)base;
-    layout(ar, w, D, N);
     const Grid g = make_grid(D, lo, hi, r);
     PMI_HIP(hipMemsetAsync(w.status, 0, 16, s));
-    PMI_LAUNCH(key_kernel<D>, n, d_X, n, g, w.keys, w.rows0);
-    size_t bytes = 0;
-    PMI_HIP(rocprim::radix_sort_pairs(nullptr, bytes, w.keys, w.keys_sorted, w.rows0, w.rows, N, 0, g.bits, s));
-    void *tmp = nullptr;
-    if ((rc = scratch(SCR_STAGE_B, bytes + 64, &tmp)) != PMI_OK) return rc;
-    PMI_HIP(rocprim::radix_sort_pairs(tmp, bytes, w.keys, w.keys_sorted, w.rows0, w.rows, N, 0, g.bits, s));
-    PMI_LAUNCH(gather_kernel<D>, n, d_X, w.keys_sorted, w.rows, n, g, w.xs, w.ys, w.zs, w.rlo, w.rhi);
+    PMI_LAUNCH(key_kernel<D>, n, s, d_X, n, g, w.keys, w.rows0);
+    if ((rc = sort_pairs(w.keys, w.keys_sorted, w.rows0, w.rows, N, g.bits, s)) != PMI_OK) return rc;
+    PMI_LAUNCH(gather_kernel<D>, n, s, d_X, w.keys_sorted, w.rows, n, g, w.xs, w.ys, w.zs, w.rlo, w.rhi);
     t = Tab{w.xs, w.ys, w.zs, w.rows, w.rlo, w.rhi, n, r2};
-    PMI_LAUNCH(count_kernel<D>, n, t, w.cnt);
-    return PMI_OK;
-}
-
-static int scan_flags(const uint32_t *flag, uint32_t *number, size_t N, hipStream_t s)
-{
-    size_t bytes = 0;
-    PMI_HIP(rocprim::exclusive_scan(nullptr, bytes, flag, number, 0u, N, rocprim::plus<uint32_t>(), s));
-    void *tmp = nullptr;
-    const int rc = scratch(SCR_STAGE_B, bytes + 64, &tmp);
-    if (rc != PMI_OK) return rc;
-    PMI_HIP(rocprim::exclusive_scan(tmp, bytes, flag, number, 0u, N, rocprim::plus<uint32_t>(), s));
+    PMI_LAUNCH(count_kernel<D>, n, s, t, w.cnt);
     return PMI_OK;
 }
 
@@ -517,8 +432,8 @@ static int scan_flags(const uint32_t *flag, uint32_t *number, size_t N, hipStrea
 static int drop_small(int32_t *lab, int32_t n, int32_t *size, int64_t min_locs, hipStream_t s)
 {
     PMI_HIP(hipMemsetAsync(size, 0, sizeof(int32_t) * (size_t)n, s));
-    PMI_LAUNCH(size_kernel, n, lab, n, size);
-    PMI_LAUNCH(size_filter_kernel, n, lab, n, size, min_locs);
+    PMI_LAUNCH(size_kernel, n, s, lab, n, size);
+    PMI_LAUNCH(size_filter_kernel, n, s, lab, n, size, min_locs);
     return PMI_OK;
 }
 
@@ -528,22 +443,21 @@ static int frame_analysis(int32_t *lab, int32_t shift, const int32_t *rows, cons
                           hipStream_t s)
 {
     const size_t G = (size_t)n_ids;
-    Arena ar;
-    void *base = nullptr;
-    const size_t bytes = 4 * 256 + G * (4 + 8 + 4 * FA_BINS + 4);
-    int rc = scratch(SCR_STAGE_C, bytes, &base);
+    unsigned long long *sum;
+    int32_t *count, *hist, *pass;
+    size_t used = 0;
+    const int rc = carve(SCR_STAGE_C, [&](Arena &ar) {
+        sum = ar.take<unsigned long long>(G);
+        count = ar.take<int32_t>(G), hist = ar.take<int32_t>(G * FA_BINS), pass = ar.take<int32_t>(G);
+    }, &used);
     if (rc != PMI_OK) return rc;
-    ar.base = (char *)base;
-    unsigned long long *sum = ar.take<unsigned long long>(G);
-    int32_t *count = ar.take<int32_t>(G), *hist = ar.take<int32_t>(G * FA_BINS), *pass = ar.take<int32_t>(G);
-    if (ar.used > bytes) { set_error("frame analysis: scratch layout"); return PMI_ERR_ARG; }
     if (d_pass) pass = d_pass;
-    PMI_HIP(hipMemsetAsync(base, 0, ar.used, s));
+    PMI_HIP(hipMemsetAsync(sum, 0, used, s));
     Edges ed;
     for (int k = 0; k <= FA_BINS; ++k) ed.e[k] = edges[k];
-    PMI_LAUNCH(fa_count_kernel, n, lab, shift, rows, d_frame, n, (int32_t)n_ids, ed, count, sum, hist);
-    PMI_LAUNCH(fa_decide_kernel, n_ids, count, sum, hist, (int32_t)n_ids, lo, hi, pass);
-    if (apply) PMI_LAUNCH(fa_apply_kernel, n, lab, shift, n, (int32_t)n_ids, pass);
+    PMI_LAUNCH(fa_count_kernel, n, s, lab, shift, rows, d_frame, n, (int32_t)n_ids, ed, count, sum, hist);
+    PMI_LAUNCH(fa_decide_kernel, n_ids, s, count, sum, hist, (int32_t)n_ids, lo, hi, pass);
+    if (apply) PMI_LAUNCH(fa_apply_kernel, n, s, lab, shift, n, (int32_t)n_ids, pass);
     return PMI_OK;
 }
 
@@ -555,7 +469,7 @@ static int counts_typed(const double *d_X, int32_t n, const double *lo, const do
     Tab t;
     int rc = prepare<D>(d_X, n, lo, hi, r, r2, w, t, s);
     if (rc != PMI_OK) return rc;
-    PMI_LAUNCH(scatter_kernel, n, w.cnt, w.rows, n, d_counts);
+    PMI_LAUNCH(scatter_kernel, n, s, w.cnt, w.rows, n, d_counts);
     return PMI_OK;
 }
 
@@ -569,14 +483,14 @@ static int smlm_typed(const double *d_X, int32_t n, const double *lo, const doub
     int rc = prepare<D>(d_X, n, lo, hi, r, r2, w, t, s);
     if (rc != PMI_OK) return rc;
     int32_t *lm = w.a, *state = w.b;
-    PMI_LAUNCH(localmax_kernel<D>, n, t, w.cnt, min_locs, lm, w.flag);
-    if ((rc = scan_flags(w.flag, w.number, (size_t)n, s)) != PMI_OK) return rc;
-    PMI_LAUNCH(fresh_kernel<D>, n, t, lm, state);
-    PMI_LAUNCH(assign_kernel<D>, n, t, state, w.number, w.lab);
+    PMI_LAUNCH(localmax_kernel<D>, n, s, t, w.cnt, min_locs, lm, w.flag);
+    if ((rc = exclusive_scan_u32<const uint32_t>(w.flag, w.number, (size_t)n, s)) != PMI_OK) return rc;
+    PMI_LAUNCH(fresh_kernel<D>, n, s, t, lm, state);
+    PMI_LAUNCH(assign_kernel<D>, n, s, t, state, w.number, w.lab);
     int32_t pending = 1;
     for (int round = 0; round < MAX_ROUNDS && pending; ++round) {
         PMI_HIP(hipMemsetAsync(w.status + 1, 0, 4, s));
-        PMI_LAUNCH(jump_kernel, n, w.lab, n, w.status + 1);
+        PMI_LAUNCH(jump_kernel, n, s, w.lab, n, w.status + 1);
         PMI_HIP(hipMemcpyAsync(&pending, w.status + 1, 4, hipMemcpyDeviceToHost, s));
         PMI_HIP(hipStreamSynchronize(s));
     }
@@ -595,7 +509,7 @@ static int smlm_typed(const double *d_X, int32_t n, const double *lo, const doub
         if ((rc = frame_analysis(w.lab, 1, w.rows, d_frame, n, n_ids, fa_lo, fa_hi, fa_edges, nullptr, true, s)) != PMI_OK)
             return rc;
     }
-    PMI_LAUNCH(scatter_kernel, n, w.lab, w.rows, n, d_labels);
+    PMI_LAUNCH(scatter_kernel, n, s, w.lab, w.rows, n, d_labels);
     return PMI_OK;
 }
 
@@ -608,13 +522,13 @@ static int dbscan_typed(const double *d_X, int32_t n, const double *lo, const do
     int rc = prepare<D>(d_X, n, lo, hi, r, r2, w, t, s);
     if (rc != PMI_OK) return rc;
     int32_t *parent = w.a, *root = w.b;
-    PMI_LAUNCH(iota_kernel, n, parent, n);
-    PMI_LAUNCH(union_kernel<D>, n, t, w.cnt, min_samples, parent, w.status);
-    PMI_LAUNCH(root_kernel, n, w.rows, w.cnt, min_samples, parent, n, root, w.flag);
-    if ((rc = scan_flags(w.flag, w.number, (size_t)n, s)) != PMI_OK) return rc;
-    PMI_LAUNCH(dbscan_label_kernel<D>, n, t, root, w.number, w.lab);
+    PMI_LAUNCH(iota_kernel, n, s, parent, nullptr, n);
+    PMI_LAUNCH(union_kernel<D>, n, s, t, w.cnt, min_samples, parent, w.status);
+    PMI_LAUNCH(root_kernel, n, s, w.rows, w.cnt, min_samples, parent, n, root, w.flag);
+    if ((rc = exclusive_scan_u32<const uint32_t>(w.flag, w.number, (size_t)n, s)) != PMI_OK) return rc;
+    PMI_LAUNCH(dbscan_label_kernel<D>, n, s, t, root, w.number, w.lab);
     if ((rc = drop_small(w.lab, n, parent, min_locs, s)) != PMI_OK) return rc;
-    PMI_LAUNCH(scatter_kernel, n, w.lab, w.rows, n, d_labels);
+    PMI_LAUNCH(scatter_kernel, n, s, w.lab, w.rows, n, d_labels);
     int32_t h_status = 0;
     PMI_HIP(hipMemcpyAsync(&h_status, w.status, 4, hipMemcpyDeviceToHost, s));
     PMI_HIP(hipStreamSynchronize(s));

@@ -32,24 +32,20 @@
 // of w = 1 / lp^2, or of column * w.  Nothing is accumulated with atomics.
 //
 // Every loop is bounded by the row count; a union that does not settle within its bound reports a status.
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-
 #include <algorithm>
 #include <type_traits>
 
-#include "pmi_common.h"
+#include "rows_common.h"
 
 #pragma clang fp contract(off)
 
 namespace pmi {
 namespace link {
 
-constexpr int BLOCK = 256;
+using namespace rows;
+
 constexpr int MAX_BINS = 8192;       // NeNA histogram in LDS: 32 KB
 constexpr int MAX_COLS = 24;
-
-static inline unsigned blocks(int64_t n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
 
 // One rounding per operation: plain operators, which the pragma above keeps from being contracted into an FMA (the
 // __f*_rn intrinsics are inline functions of a header compiled with contraction allowed, and __fsqrt_rn is the
@@ -60,17 +56,6 @@ template <typename T> __device__ __forceinline__ T add_rn(T a, T b) { return a +
 template <typename T> __device__ __forceinline__ T div_rn(T a, T b) { return a / b; }
 __device__ __forceinline__ float sqrt_rn(float a) { return __builtin_sqrtf(a); }
 __device__ __forceinline__ double sqrt_rn(double a) { return __builtin_sqrt(a); }
-
-// first row in [from, n) whose frame is >= v (sorted column): at most 40 halvings for n < 2^31
-__device__ __forceinline__ int32_t lower_bound(const int64_t *__restrict__ frame, int32_t from, int32_t n, int64_t v)
-{
-    int32_t lo = from, hi = n;
-    for (int it = 0; it < 40 && lo < hi; ++it) {
-        const int32_t mid = lo + ((hi - lo) >> 1);
-        if (frame[mid] < v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
 
 __global__ void frame_index_kernel(const int64_t *__restrict__ frame, int32_t n, int64_t k, int32_t *__restrict__ lo,
                                    int32_t *__restrict__ hi)
@@ -110,30 +95,6 @@ struct Pair {
     }
 };
 
-__device__ __forceinline__ int32_t find_root(const int32_t *parent, int32_t v, int32_t n)
-{
-    // a parent is always a lower row: at most n steps
-    for (int32_t it = 0; it < n; ++it) {
-        const int32_t p = __hip_atomic_load(parent + v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (p == v) return v;
-        v = p;
-    }
-    return v;
-}
-
-// status[0] is set when a union did not settle
-__device__ __forceinline__ void unite(int32_t *parent, int32_t a, int32_t b, int32_t n, int32_t *status)
-{
-    for (int32_t it = 0; it < n; ++it) {
-        a = find_root(parent, a, n);
-        b = find_root(parent, b, n);
-        if (a == b) return;
-        const int32_t low = min(a, b), high = max(a, b);
-        if (atomicCAS(parent + high, high, low) == high) return;
-    }
-    atomicExch(status, 1);
-}
-
 template <typename TX, typename TY>
 __global__ void union_kernel(const int64_t *__restrict__ frame, const TX *__restrict__ x, const TY *__restrict__ y,
                              const int64_t *__restrict__ group, const int32_t *__restrict__ lo,
@@ -156,14 +117,6 @@ __global__ void union_kernel(const int64_t *__restrict__ frame, const TX *__rest
     }
 }
 
-__global__ void iota_kernel(int32_t *a, int32_t *b, int32_t n)
-{
-    const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n) return;
-    a[i] = (int32_t)i;
-    if (b) b[i] = (int32_t)i;
-}
-
 __global__ void root_kernel(const int32_t *__restrict__ parent, int32_t n, uint32_t *__restrict__ root,
                             int32_t *__restrict__ start_of)
 {
@@ -171,17 +124,6 @@ __global__ void root_kernel(const int32_t *__restrict__ parent, int32_t n, uint3
     if (i >= n) return;
     root[i] = (uint32_t)find_root(parent, (int32_t)i, n);
     start_of[i] = -1;
-}
-
-// first position in [0, n) of the sorted keys that is >= v
-__device__ __forceinline__ int32_t key_lower_bound(const uint32_t *__restrict__ keys, int32_t n, uint32_t v)
-{
-    int32_t lo = 0, hi = n;
-    for (int it = 0; it < 40 && lo < hi; ++it) {
-        const int32_t mid = lo + ((hi - lo) >> 1);
-        if (keys[mid] < v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
 }
 
 // One lane per component (the lane of its root row): the reference's loop over the component's rows `rows[p0 .. p1)`,
@@ -196,10 +138,10 @@ __global__ void replay_kernel(const int64_t *__restrict__ frame, const TX *__res
     const int64_t r64 = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (r64 >= n) return;
     const int32_t r = (int32_t)r64;
-    const int32_t p0 = key_lower_bound(sorted_root, n, (uint32_t)r);
+    const int32_t p0 = lower_bound(sorted_root, 0, n, (uint32_t)r);
     if (p0 >= n || sorted_root[p0] != (uint32_t)r) return;          // r is not a root
     int32_t p1 = p0 + 1;
-    if (p1 < n && sorted_root[p1] == (uint32_t)r) p1 = key_lower_bound(sorted_root, n, (uint32_t)r + 1u);
+    if (p1 < n && sorted_root[p1] == (uint32_t)r) p1 = lower_bound(sorted_root, 0, n, (uint32_t)r + 1u);
     for (int32_t s = p0; s < p1; ++s) {
         const int32_t first = rows[s];
         if (start_of[first] != -1) continue;
@@ -347,8 +289,8 @@ __global__ void combine_kernel(const uint32_t *__restrict__ sorted_group, const 
     const int64_t g64 = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (g64 >= n_groups) return;
     const int32_t g = (int32_t)g64;
-    const int32_t p0 = key_lower_bound(sorted_group, n, (uint32_t)g);
-    const int32_t p1 = key_lower_bound(sorted_group, n, (uint32_t)g + 1u);
+    const int32_t p0 = lower_bound(sorted_group, 0, n, (uint32_t)g);
+    const int32_t p1 = lower_bound(sorted_group, 0, n, (uint32_t)g + 1u);
     count[g] = (uint32_t)(p1 - p0);
     int64_t fmin = INT64_MAX, fmax = INT64_MIN;
     if (frame)
@@ -381,21 +323,6 @@ __global__ void combine_kernel(const uint32_t *__restrict__ sorted_group, const 
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------
-// one scratch slot cut into 256-byte aligned pieces
-struct Arena {
-    char *base = nullptr;
-    size_t used = 0, size = 0;
-    template <typename T>
-    T *take(size_t count)
-    {
-        const size_t bytes = (count * sizeof(T) + 255) & ~size_t(255);
-        T *p = (T *)(base + used);
-        used += bytes;
-        return used <= size ? p : nullptr;
-    }
-};
-static size_t piece(size_t count, size_t el) { return (count * el + 255) & ~size_t(255); }
-
 static int check_rows(const char *what, int64_t n)
 {
     if (n < 0 || n > INT32_MAX - 1) {
@@ -417,8 +344,7 @@ static int check_xy(const char *what, int x_type, int y_type)
 static int frame_index(const int64_t *d_frame, int32_t n, int64_t k, int32_t *lo, int32_t *hi, hipStream_t s)
 {
     if (n == 0) return PMI_OK;
-    frame_index_kernel<<<blocks(n), BLOCK, 0, s>>>(d_frame, n, k, lo, hi);
-    PMI_HIP(hipGetLastError());
+    PMI_LAUNCH(frame_index_kernel, n, s, d_frame, n, k, lo, hi);
     return PMI_OK;
 }
 
@@ -428,13 +354,7 @@ static int sort_rows(uint32_t *keys, uint32_t *keys_out, int32_t *rows, int32_t 
 {
     int bits = 1;
     while (bits < 32 && (int64_t(1) << bits) < key_end) bits++;
-    size_t bytes = 0;
-    PMI_HIP(rocprim::radix_sort_pairs(nullptr, bytes, keys, keys_out, rows, rows_out, (size_t)n, 0, bits, s));
-    void *tmp = nullptr;
-    const int rc = scratch(SCR_STAGE_B, bytes + 64, &tmp);
-    if (rc != PMI_OK) return rc;
-    PMI_HIP(rocprim::radix_sort_pairs(tmp, bytes, keys, keys_out, rows, rows_out, (size_t)n, 0, bits, s));
-    return PMI_OK;
+    return sort_pairs(keys, keys_out, rows, rows_out, (size_t)n, bits, s);
 }
 
 template <typename TX, typename TY>
@@ -442,40 +362,28 @@ static int groups_typed(const TX *x, const TY *y, const int64_t *frame, const in
                         int64_t k, int32_t *link_group, int64_t *n_groups, hipStream_t s)
 {
     const size_t N = (size_t)n;
-    Arena ar;
-    ar.size = 9 * piece(N, 4) + piece(4, 4);
-    void *base = nullptr;
-    int rc = scratch(SCR_STAGE_A, ar.size, &base);
+    int32_t *lo, *hi, *parent, *rows, *rows_sorted, *start_of, *status;
+    uint32_t *root, *root_sorted, *rank;
+    int rc = carve(SCR_STAGE_A, [&](Arena &ar) {
+        lo = ar.take<int32_t>(N), hi = ar.take<int32_t>(N), parent = ar.take<int32_t>(N);
+        root = ar.take<uint32_t>(N), root_sorted = ar.take<uint32_t>(N);
+        rows = ar.take<int32_t>(N), rows_sorted = ar.take<int32_t>(N), start_of = ar.take<int32_t>(N);
+        rank = ar.take<uint32_t>(N);
+        status = ar.take<int32_t>(4);
+    });
     if (rc != PMI_OK) return rc;
-    ar.base = (char *)base;
-    int32_t *lo = ar.take<int32_t>(N), *hi = ar.take<int32_t>(N), *parent = ar.take<int32_t>(N);
-    uint32_t *root = ar.take<uint32_t>(N), *root_sorted = ar.take<uint32_t>(N);
-    int32_t *rows = ar.take<int32_t>(N), *rows_sorted = ar.take<int32_t>(N), *start_of = ar.take<int32_t>(N);
-    uint32_t *rank = ar.take<uint32_t>(N);
-    int32_t *status = ar.take<int32_t>(4);
-    if (!status) { set_error("pmi_link_groups_dev: scratch layout"); return PMI_ERR_ARG; }
     uint32_t *flag = root;                                          // the roots are dead once they are sorted
 
     PMI_HIP(hipMemsetAsync(status, 0, 16, s));
     if ((rc = frame_index(frame, n, k, lo, hi, s)) != PMI_OK) return rc;
-    iota_kernel<<<blocks(n), BLOCK, 0, s>>>(parent, rows, n);
-    PMI_HIP(hipGetLastError());
-    union_kernel<TX, TY><<<blocks(n), BLOCK, 0, s>>>(frame, x, y, group, lo, hi, n, k, r2, parent, status);
-    PMI_HIP(hipGetLastError());
-    root_kernel<<<blocks(n), BLOCK, 0, s>>>(parent, n, root, start_of);
-    PMI_HIP(hipGetLastError());
+    PMI_LAUNCH(iota_kernel, n, s, parent, rows, n);
+    PMI_LAUNCH((union_kernel<TX, TY>), n, s, frame, x, y, group, lo, hi, n, k, r2, parent, status);
+    PMI_LAUNCH(root_kernel, n, s, parent, n, root, start_of);
     if ((rc = sort_rows(root, root_sorted, rows, rows_sorted, n, n, s)) != PMI_OK) return rc;
-    replay_kernel<TX, TY><<<blocks(n), BLOCK, 0, s>>>(frame, x, y, group, lo, hi, n, k, r2, root_sorted, rows_sorted, start_of);
-    PMI_HIP(hipGetLastError());
-    start_flag_kernel<<<blocks(n), BLOCK, 0, s>>>(start_of, n, flag);
-    PMI_HIP(hipGetLastError());
-    size_t bytes = 0;
-    PMI_HIP(rocprim::exclusive_scan(nullptr, bytes, flag, rank, 0u, N, rocprim::plus<uint32_t>(), s));
-    void *tmp = nullptr;
-    if ((rc = scratch(SCR_STAGE_B, bytes + 64, &tmp)) != PMI_OK) return rc;
-    PMI_HIP(rocprim::exclusive_scan(tmp, bytes, flag, rank, 0u, N, rocprim::plus<uint32_t>(), s));
-    label_kernel<<<blocks(n), BLOCK, 0, s>>>(start_of, rank, n, link_group, status);
-    PMI_HIP(hipGetLastError());
+    PMI_LAUNCH((replay_kernel<TX, TY>), n, s, frame, x, y, group, lo, hi, n, k, r2, root_sorted, rows_sorted, start_of);
+    PMI_LAUNCH(start_flag_kernel, n, s, start_of, n, flag);
+    if ((rc = exclusive_scan_u32(flag, rank, N, s)) != PMI_OK) return rc;
+    PMI_LAUNCH(label_kernel, n, s, start_of, rank, n, link_group, status);
     int32_t h_status = 0;
     uint32_t h_rank = 0, h_flag = 0;
     PMI_HIP(hipMemcpyAsync(&h_status, status, 4, hipMemcpyDeviceToHost, s));
@@ -498,14 +406,9 @@ static int nena_typed(const TX *x, const TY *y, const int64_t *frame, const int6
     PMI_HIP(hipMemsetAsync(hist, 0, sizeof(unsigned long long) * n_bins, s));
     const int32_t n_visit = 100 * (int32_t)((double)n / 100.0);     // the reference's 100 * int(N / 100)
     if (n_visit == 0) return PMI_OK;
-    Arena ar;
-    ar.size = 2 * piece((size_t)n, 4);
-    void *base = nullptr;
-    int rc = scratch(SCR_STAGE_A, ar.size, &base);
+    int32_t *lo, *hi;
+    int rc = carve(SCR_STAGE_A, [&](Arena &ar) { lo = ar.take<int32_t>(n), hi = ar.take<int32_t>(n); });
     if (rc != PMI_OK) return rc;
-    ar.base = (char *)base;
-    int32_t *lo = ar.take<int32_t>(n), *hi = ar.take<int32_t>(n);
-    if (!hi) { set_error("pmi_nena_hist_dev: scratch layout"); return PMI_ERR_ARG; }
     if ((rc = frame_index(frame, n, 1, lo, hi, s)) != PMI_OK) return rc;
     const unsigned grid = (unsigned)std::min<int64_t>(blocks(n_visit), 8 * (int64_t)device_cu_count());
     nena_kernel<TX, TY><<<grid, BLOCK, sizeof(uint32_t) * n_bins, s>>>(frame, x, y, group, lo, hi, n, n_visit, d_max,
@@ -584,27 +487,22 @@ int pmi_link_combine_dev(const int32_t *d_link_group, int64_t n, int64_t n_group
     if (n_groups == 0) return PMI_OK;
     hipStream_t s = (hipStream_t)stream;
     const size_t N = std::max<size_t>((size_t)n, 1);
-    link::Arena ar;
-    ar.size = 4 * link::piece(N, 4);
-    void *base = nullptr;
-    if ((rc = scratch(SCR_STAGE_A, ar.size, &base)) != PMI_OK) return rc;
-    ar.base = (char *)base;
-    uint32_t *keys = ar.take<uint32_t>(N), *keys_sorted = ar.take<uint32_t>(N);
-    int32_t *rows = ar.take<int32_t>(N), *rows_sorted = ar.take<int32_t>(N);
-    if (!rows_sorted) { set_error("pmi_link_combine_dev: scratch layout"); return PMI_ERR_ARG; }
+    uint32_t *keys, *keys_sorted;
+    int32_t *rows, *rows_sorted;
+    rc = rows::carve(SCR_STAGE_A, [&](rows::Arena &ar) {
+        keys = ar.take<uint32_t>(N), keys_sorted = ar.take<uint32_t>(N);
+        rows = ar.take<int32_t>(N), rows_sorted = ar.take<int32_t>(N);
+    });
+    if (rc != PMI_OK) return rc;
     if (n > 0) {
         // a link group is an index below n_groups: a negative or larger value becomes n_groups, sorts behind every group
         // and is not summed; the sort then needs only the bits of n_groups
-        link::group_key_kernel<<<link::blocks(n), link::BLOCK, 0, s>>>(d_link_group, (int32_t)n, (int32_t)n_groups, keys);
-        PMI_HIP(hipGetLastError());
-        link::iota_kernel<<<link::blocks(n), link::BLOCK, 0, s>>>(rows, nullptr, (int32_t)n);
-        PMI_HIP(hipGetLastError());
+        PMI_LAUNCH(link::group_key_kernel, n, s, d_link_group, (int32_t)n, (int32_t)n_groups, keys);
+        PMI_LAUNCH(rows::iota_kernel, n, s, rows, nullptr, (int32_t)n);
         if ((rc = link::sort_rows(keys, keys_sorted, rows, rows_sorted, (int32_t)n, n_groups + 1, s)) != PMI_OK) return rc;
     }
-    link::combine_kernel<<<link::blocks(n_groups), link::BLOCK, 0, s>>>(keys_sorted, rows_sorted, (int32_t)n,
-                                                                          (int32_t)n_groups, d_frame, cols, d_count,
-                                                                          d_first, d_last, d_last_row);
-    PMI_HIP(hipGetLastError());
+    PMI_LAUNCH(link::combine_kernel, n_groups, s, keys_sorted, rows_sorted, (int32_t)n, (int32_t)n_groups, d_frame, cols,
+               d_count, d_first, d_last, d_last_row);
     return PMI_OK;
 }
 

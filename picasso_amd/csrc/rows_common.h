@@ -1,0 +1,143 @@
+// rows_common.h — what the kernels over a resident localization table share (aim.hip, link.hip, cluster.hip): launch
+// shape, bisection, union-find, the scratch arena and the rocPRIM sorts and scan.  It pulls in rocPRIM: only those
+// three sources include it, the fit kernels do not pay for it.
+#pragma once
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
+
+#include "pmi_common.h"
+
+namespace pmi {
+namespace rows {
+
+constexpr int BLOCK = 256;
+
+static inline unsigned blocks(int64_t n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
+
+// one lane per row of `count`, on `stream`; a kernel name with a comma goes in parentheses
+#define PMI_LAUNCH(kernel, count, stream, ...)                                                    \
+    do {                                                                                          \
+        kernel<<<pmi::rows::blocks(count), pmi::rows::BLOCK, 0, stream>>>(__VA_ARGS__);           \
+        PMI_HIP(hipGetLastError());                                                               \
+    } while (0)
+
+// first position in [from, n) of the sorted array that is >= v: at most 40 halvings for n < 2^31
+template <typename T>
+__device__ __forceinline__ int32_t lower_bound(const T *__restrict__ a, int32_t from, int32_t n, T v)
+{
+    int32_t lo = from, hi = n;
+    for (int it = 0; it < 40 && lo < hi; ++it) {
+        const int32_t mid = lo + ((hi - lo) >> 1);
+        if (a[mid] < v) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// Union-find over rows.  parent[] starts as the identity (iota_kernel); unions may run concurrently from any lane of
+// the device, reads of roots come in a later kernel.
+__device__ __forceinline__ int32_t find_root(const int32_t *parent, int32_t v, int32_t n)
+{
+    // a parent is always a lower row: at most n steps
+    for (int32_t it = 0; it < n; ++it) {
+        const int32_t p = __hip_atomic_load(parent + v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (p == v) return v;
+        v = p;
+    }
+    return v;
+}
+
+// status[0] is set when a union did not settle
+__device__ __forceinline__ void unite(int32_t *parent, int32_t a, int32_t b, int32_t n, int32_t *status)
+{
+    for (int32_t it = 0; it < n; ++it) {
+        a = find_root(parent, a, n);
+        b = find_root(parent, b, n);
+        if (a == b) return;
+        const int32_t low = min(a, b), high = max(a, b);
+        if (atomicCAS(parent + high, high, low) == high) return;
+    }
+    atomicExch(status, 1);
+}
+
+// static: each of the including sources registers its own copy
+static __global__ void iota_kernel(int32_t *a, int32_t *b /* may be null */, int32_t n)
+{
+    const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    a[i] = (int32_t)i;
+    if (b) b[i] = (int32_t)i;
+}
+
+// ---- host ------------------------------------------------------------------------------------------------------
+// one scratch slot cut into 256-byte aligned pieces; without a base it only measures
+struct Arena {
+    char *base = nullptr;
+    size_t used = 0;
+    template <typename T>
+    T *take(size_t count)
+    {
+        T *p = base ? (T *)(base + used) : nullptr;
+        used += (count * sizeof(T) + 255) & ~size_t(255);
+        return p;
+    }
+};
+
+// layout(Arena &) takes every piece of a call, in one order: it runs once to measure and once on the slot's buffer,
+// so the size asked for is the size used.  The pieces start at the first one taken and span *used bytes.
+template <typename Layout>
+static int carve(int slot, Layout &&layout, size_t *used = nullptr)
+{
+    Arena measure;
+    layout(measure);
+    void *base = nullptr;
+    const int rc = scratch(slot, measure.used, &base);
+    if (rc != PMI_OK) return rc;
+    Arena place;
+    place.base = (char *)base;
+    layout(place);
+    if (used) *used = place.used;
+    return PMI_OK;
+}
+
+// The rocPRIM calls; each takes its temporary from SCR_STAGE_B, which no arena of these modules is carved from.
+// Stable radix sorts on the low `bits` of the keys.
+template <typename K, typename V>
+static int sort_pairs(K *keys, K *keys_out, V *vals, V *vals_out, size_t n, int bits, hipStream_t stream)
+{
+    size_t bytes = 0;
+    PMI_HIP(rocprim::radix_sort_pairs(nullptr, bytes, keys, keys_out, vals, vals_out, n, 0, bits, stream));
+    void *tmp = nullptr;
+    const int rc = scratch(SCR_STAGE_B, bytes + 64, &tmp);
+    if (rc != PMI_OK) return rc;
+    PMI_HIP(rocprim::radix_sort_pairs(tmp, bytes, keys, keys_out, vals, vals_out, n, 0, bits, stream));
+    return PMI_OK;
+}
+
+template <typename K>
+static int sort_keys(K *keys, K *keys_out, size_t n, int bits, hipStream_t stream)
+{
+    size_t bytes = 0;
+    PMI_HIP(rocprim::radix_sort_keys(nullptr, bytes, keys, keys_out, n, 0, bits, stream));
+    void *tmp = nullptr;
+    const int rc = scratch(SCR_STAGE_B, bytes + 64, &tmp);
+    if (rc != PMI_OK) return rc;
+    PMI_HIP(rocprim::radix_sort_keys(tmp, bytes, keys, keys_out, n, 0, bits, stream));
+    return PMI_OK;
+}
+
+// out[i] = flag[0] + ... + flag[i - 1].  F is uint32_t or const uint32_t; a template, like the sorts, so that a source
+// that does not scan carries no scan kernels.
+template <typename F>
+static int exclusive_scan_u32(F *flag, uint32_t *out, size_t n, hipStream_t stream)
+{
+    size_t bytes = 0;
+    PMI_HIP(rocprim::exclusive_scan(nullptr, bytes, flag, out, 0u, n, rocprim::plus<uint32_t>(), stream));
+    void *tmp = nullptr;
+    const int rc = scratch(SCR_STAGE_B, bytes + 64, &tmp);
+    if (rc != PMI_OK) return rc;
+    PMI_HIP(rocprim::exclusive_scan(tmp, bytes, flag, out, 0u, n, rocprim::plus<uint32_t>(), stream));
+    return PMI_OK;
+}
+
+}  // namespace rows
+}  // namespace pmi
