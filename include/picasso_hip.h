@@ -53,6 +53,10 @@
  *                      uses them, :1212-1272 _nfndh / _fill_dnfl
  *   pmi_cluster_*      picasso/clusterer.py:114-201 _cluster (the SMLM clusterer),
  *                      :34-111 _frame_analysis / frame_analysis, :410-445 _dbscan
+ *   pmi_pairs_*        picasso/postprocess.py:37-94 get_index_blocks, :169-204
+ *                      _fill_index_blocks, :1543-1579 _local_density (:1582-1631
+ *                      compute_local_density), :960-999 _distance_histogram
+ *                      (:1002-1055 distance_histogram, :1505-1540 pair_correlation)
  */
 #ifndef PICASSO_HIP_H
 #define PICASSO_HIP_H
@@ -542,6 +546,35 @@ int pmi_cluster_dbscan_dev(const double *d_X, int dims, int64_t n, const double 
                            double r2, int64_t min_samples, int64_t min_locs, int32_t *d_labels, void *stream);
 int pmi_cluster_frame_analysis_dev(const int32_t *d_ids, const int64_t *d_frame, int64_t n, int64_t n_ids, double fa_lo,
                                    double fa_hi, const double *fa_edges, int32_t *d_pass, void *stream);
+
+/* ---- local density and the distance histogram (picasso/postprocess.py:37-204, :960-999, :1543-1579, csrc/pairs.hip) - *
+ * A table binned into square blocks of the search radius: d_x_index / d_y_index (uint32, computed on the host as the
+ * reference does), K x L blocks.  d_x / d_y are the table's columns IN THE CALLER'S ROW ORDER, float32 or float64
+ * (PMI_LINK_F32 / PMI_LINK_F64, each on its own).  At most 2^31 - 2 rows; memory is O(n) whatever K x L is (no block
+ * table: a block's rows are two bisections of the sorted keys).  Scratch comes from the library's arena; every call runs
+ * on `stream` and synchronises it before it returns.
+ *
+ * pmi_pairs_order_dev    d_rows[q] (int32) = the row at sorted position q, equal to np.lexsort([x_index, y_index]);
+ *                        d_keys[q] (uint64) = y_index << 32 | x_index of that row; *p = the first sorted position whose
+ *                        block lies outside the grid (n when there is none): the reference's block table stops filling
+ *                        there, so only the positions < p are ever found as neighbours.
+ * pmi_pairs_density_dev  d_density[q] (uint32) of sorted position q < n: the positions j < p in the nine blocks
+ *                        (ki - 1 .. ki + 1, li - 1 .. li + 1) with dx2 < r2, dy2 < r2 and dx2 + dy2 < r2, q itself
+ *                        included when q < p.  A block index of -1 is K - 1 / L - 1 (a negative index in the reference:
+ *                        with K or L <= 2 a block is counted twice); an index >= K / L is an empty block (the reference
+ *                        reads outside its table there).  r2 = radius ** 2.
+ * pmi_pairs_distance_hist_dev  d_hist[n_bins] (uint64, device): the pairs of positions a < b < p with block(b) - block(a)
+ *                        one of (0, 0), (0, 1), (1, 0), (1, 1) -- (1, -1) is not visited, as in the reference -- and
+ *                        dx2 < r2, dy2 < r2, d = sqrt(dx2 + dy2) < r_max, bin floor(d / bin_size) < n_bins.  Up to 8192
+ *                        bins are counted in LDS, more with one integer atomic per pair.  r2 = r_max ** 2. */
+int pmi_pairs_order_dev(const uint32_t *d_x_index, const uint32_t *d_y_index, int64_t n, int64_t K, int64_t L,
+                        int32_t *d_rows, uint64_t *d_keys, int64_t *p, void *stream);
+int pmi_pairs_density_dev(const void *d_x, int x_type, const void *d_y, int y_type, const int32_t *d_rows,
+                          const uint64_t *d_keys, int64_t n, int64_t p, int64_t K, int64_t L, double r2,
+                          uint32_t *d_density, void *stream);
+int pmi_pairs_distance_hist_dev(const void *d_x, int x_type, const void *d_y, int y_type, const int32_t *d_rows,
+                                const uint64_t *d_keys, int64_t n, int64_t p, int64_t K, int64_t L, double r_max,
+                                double r2, double bin_size, int64_t n_bins, uint64_t *d_hist, void *stream);
 
 /* ---- timing hooks for bench.py (HIP events on the given stream) ------- */
 int pmi_event_create(void **event);

@@ -912,3 +912,62 @@ def cluster_frame_analysis(ids, frame, n_ids: int, fa_lo: float, fa_hi: float, f
             _dptr(d_ids), _dptr(d_frame), len(ids), int(n_ids), float(fa_lo), float(fa_hi), _lib.ptr(edges),
             _dptr(passed), ctypes.c_void_p(stream)), "pmi_cluster_frame_analysis_dev")
         return passed[:int(n_ids)].cpu().numpy()
+
+
+# ---- local density and the distance histogram (csrc/pairs.hip, picasso/postprocess.py:37-204, :960-999, :1543-1579) ----
+class BlockTable:
+    """A table in the block order of the reference's get_index_blocks: the uint32 block indices go to the device once
+    and are sorted there (pmi_pairs_order_dev); `rows` is then np.lexsort([x_index, y_index]) and `p` the sorted
+    position at which the reference's block table stops filling (n when every row lies inside the K x L grid)."""
+
+    def __init__(self, x_index, y_index, K: int, L: int):
+        import torch
+        _lib.require_gpu()
+        x_index, y_index = np.asarray(x_index), np.asarray(y_index)
+        if x_index.dtype != np.uint32 or y_index.dtype != np.uint32 or x_index.shape != y_index.shape or x_index.ndim != 1:
+            raise TypeError("x_index and y_index must be uint32 arrays of one length")
+        self.n, self.K, self.L = int(len(x_index)), int(K), int(L)
+        d_xi, d_yi = _to_device(x_index), _to_device(y_index)
+        self.device = d_xi.device
+        self.stream = torch.cuda.current_stream(self.device).cuda_stream
+        self.rows = torch.empty(max(self.n, 1), dtype=torch.int32, device=self.device)
+        self.keys = torch.empty(max(self.n, 1), dtype=torch.int64, device=self.device)
+        p = ctypes.c_int64(0)
+        with _lib.lock():
+            _lib.check(_lib.load().pmi_pairs_order_dev(_dptr(d_xi), _dptr(d_yi), self.n, self.K, self.L, _dptr(self.rows),
+                                                       _dptr(self.keys), ctypes.byref(p), ctypes.c_void_p(self.stream)),
+                       "pmi_pairs_order_dev")
+        self.p = int(p.value)
+
+    def order(self) -> np.ndarray:
+        """The int64 permutation into block order."""
+        return self.rows[:self.n].cpu().numpy().astype(np.int64)
+
+    def _columns(self, x, y):
+        x, y = np.asarray(x), np.asarray(y)
+        if len(x) != self.n or len(y) != self.n:
+            raise ValueError("x and y must have one entry per row of the table")
+        return _to_device(x), link_type(x.dtype, True), _to_device(y), link_type(y.dtype, True)
+
+    def density(self, x, y, r2: float) -> np.ndarray:
+        """uint32 neighbour count of every row, in block order; x / y in the caller's row order."""
+        import torch
+        d_x, tx, d_y, ty = self._columns(x, y)
+        out = torch.zeros(max(self.n, 1), dtype=torch.int32, device=self.device)
+        with _lib.lock():
+            _lib.check(_lib.load().pmi_pairs_density_dev(
+                _dptr(d_x), tx, _dptr(d_y), ty, _dptr(self.rows), _dptr(self.keys), self.n, self.p, self.K, self.L,
+                float(r2), _dptr(out), ctypes.c_void_p(self.stream)), "pmi_pairs_density_dev")
+            return out[:self.n].cpu().numpy().view(np.uint32)
+
+    def distance_hist(self, x, y, r_max: float, r2: float, bin_size: float, n_bins: int) -> np.ndarray:
+        """uint64 counts of the distance histogram."""
+        import torch
+        d_x, tx, d_y, ty = self._columns(x, y)
+        hist = torch.zeros(max(int(n_bins), 1), dtype=torch.int64, device=self.device)
+        with _lib.lock():
+            _lib.check(_lib.load().pmi_pairs_distance_hist_dev(
+                _dptr(d_x), tx, _dptr(d_y), ty, _dptr(self.rows), _dptr(self.keys), self.n, self.p, self.K, self.L,
+                float(r_max), float(r2), float(bin_size), int(n_bins), _dptr(hist), ctypes.c_void_p(self.stream)),
+                "pmi_pairs_distance_hist_dev")
+            return hist[:int(n_bins)].cpu().numpy().view(np.uint64)

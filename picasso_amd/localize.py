@@ -838,7 +838,8 @@ def install(picasso_localize=None, picasso_gaussmle=None, picasso_gausslq=None, 
     undrift (``aim``, ``intersection_max``, ``intersection_max_z``), which the Localize GUI, Render and
     `picasso aim` call.  ``picasso.postprocess`` also gets ``link``, ``nena`` and the functions under them
     (``postprocess.LINK_NENA_NAMES``), and ``picasso.localize`` the two quick checks built on them, ``check_nena`` and
-    ``check_kinetics``.  ``picasso_clusterer`` (default: ``picasso.clusterer`` when it imports) gets DBSCAN, the SMLM
+    ``check_kinetics``, and the local density, distance histogram and pair correlation (``postprocess.PAIR_NAMES``).
+    ``picasso_clusterer`` (default: ``picasso.clusterer`` when it imports) gets DBSCAN, the SMLM
     clusterer and the frame analysis (``clusterer.CLUSTERER_NAMES``); HDBSCAN and the cluster statistics stay its own."""
     if picasso_localize is None:
         import picasso.localize as picasso_localize       # the installed reference
@@ -894,7 +895,7 @@ def install(picasso_localize=None, picasso_gaussmle=None, picasso_gausslq=None, 
     picasso_postprocess = _reference_module(picasso_postprocess, "postprocess")
     if picasso_postprocess is not None:
         from . import postprocess as amd_pp
-        for name in ("segment", "undrift") + amd_pp.LINK_NENA_NAMES:
+        for name in ("segment", "undrift") + amd_pp.LINK_NENA_NAMES + amd_pp.PAIR_NAMES:
             setattr(picasso_postprocess, name, getattr(amd_pp, name))
     picasso_aim = _reference_module(picasso_aim, "aim")
     if picasso_aim is not None:

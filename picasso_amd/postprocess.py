@@ -2,7 +2,9 @@
 ``n_segments``, ``segment``, ``undrift``; :3157-3218 ``_apply_drift`` / ``apply_drift``) on top of
 the GPU render (csrc/render.hip) and cross-correlation (csrc/xcorr.hip), and linking and NeNA
 (:2007-2071 ``link``, :2422-2821 the link groups and their combination, :1058-1119 ``nena``, :1165-1239 the
-next-frame neighbour distance histogram) on top of csrc/link.hip.
+next-frame neighbour distance histogram) on top of csrc/link.hip, and the local density, the distance histogram and the
+pair correlation (:37-204 the index blocks, :1582-1631 ``compute_local_density``, :1002-1055 ``distance_histogram``,
+:1505-1540 ``pair_correlation``) on top of csrc/pairs.hip.
 """
 from __future__ import annotations
 
@@ -21,6 +23,8 @@ from . import backend, imageprocess, lib, render
 # what localize.install() rebinds on picasso.postprocess besides segment / undrift
 LINK_NENA_NAMES = ("link", "_get_link_groups", "get_link_groups", "_link_loc_groups", "link_loc_groups", "nena",
                    "_next_frame_neighbor_distance_histogram", "next_frame_neighbor_distance_histogram")
+# ... and for the analyses over the index blocks
+PAIR_NAMES = ("_index_blocks_shape", "compute_local_density", "distance_histogram", "pair_correlation")
 _SEGMENT_RENDER = {"blur_method": "gaussian", "min_blur_width": 1}      # what undrift renders its segments with
 
 
@@ -349,3 +353,57 @@ def nena(locs: pd.DataFrame, info=None, callback: Callable[[int], None] | None =
         "pixelsize": lib.get_from_metadata(info, "Pixelsize", default="N/A"),
     }
     return result, s
+
+
+# ---- local density, distance histogram, pair correlation (postprocess.py:37-204, :960-1055, :1505-1631) ----------
+def _index_blocks_shape(info, size: float) -> tuple[int, int]:
+    """(blocks in y, blocks in x) of the index grid (postprocess.py:108-129)."""
+    width = lib.get_from_metadata(info, "Width", raise_error=True)
+    height = lib.get_from_metadata(info, "Height", raise_error=True)
+    return int(np.ceil(height / size)), int(np.ceil(width / size))
+
+
+def _index_blocks(locs: pd.DataFrame, info, size: float):
+    """The host part of get_index_blocks (postprocess.py:74-83), as the reference's own NumPy calls, and the sort on
+    the device instead of the K x L block table -> (sanity-filtered locs, backend.BlockTable).  The reference splits
+    the rows into int(N / n_threads)-row chunks and so raises on an empty table (range() with step 0) on every
+    machine; here that is the only table not computed."""
+    locs = lib.ensure_sanity(locs, info)
+    x_index = np.uint32(locs["x"].to_numpy() / size)
+    y_index = np.uint32(locs["y"].to_numpy() / size)
+    n_blocks_y, n_blocks_x = _index_blocks_shape(info, size)
+    if len(locs) == 0:
+        raise ValueError("range() arg 3 must not be zero")
+    return locs, backend.BlockTable(x_index, y_index, n_blocks_y, n_blocks_x)
+
+
+def compute_local_density(locs: pd.DataFrame, info, radius: float) -> pd.DataFrame:
+    """The localizations in block order with the column ``density``: the number of localizations within ``radius``,
+    the row itself included (postprocess.py:1582-1631).  Counted as the reference counts: a row whose block index
+    falls outside the grid (x / radius rounds up to Width / radius) and every row sorted behind it is never a
+    neighbour, and a block index of -1 is the last block row / column."""
+    locs, table = _index_blocks(locs, info, radius)
+    density = table.density(locs["x"].to_numpy(), locs["y"].to_numpy(), _squared_like_numba(radius))
+    locs = locs.iloc[table.order()]
+    locs["density"] = density.astype(np.uint64)        # np.sum over the reference's per-thread uint32 arrays
+    return locs
+
+
+def distance_histogram(locs: pd.DataFrame, info, bin_size: float, r_max: float) -> np.ndarray:
+    """uint64 histogram of the pairwise distances below ``r_max`` (postprocess.py:1002-1055), uint32(r_max / bin_size)
+    bins.  As in the reference, a pair is counted when the later row (in block order) lies in the same block or in
+    the block to the right, below or below right of the earlier one: pairs across the lower-left diagonal are not."""
+    locs, table = _index_blocks(locs, info, r_max)
+    n_bins = int(np.uint32(r_max / bin_size))
+    return table.distance_hist(locs["x"].to_numpy(), locs["y"].to_numpy(), r_max, _squared_like_numba(r_max), bin_size,
+                               n_bins)
+
+
+def pair_correlation(locs: pd.DataFrame, info, bin_size: float, r_max: float):
+    """-> (bins_lower, pc): the distance histogram divided by the area of each ring (postprocess.py:1505-1540)."""
+    dh = distance_histogram(locs, info, bin_size, r_max)
+    bins_lower = np.arange(bin_size, r_max + bin_size, bin_size)
+    if bins_lower.shape[0] > dh.shape[0]:
+        bins_lower = bins_lower[:-1]
+    area = np.pi * bin_size * (2 * bins_lower + bin_size)
+    return bins_lower, dh / area
