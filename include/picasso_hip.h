@@ -53,6 +53,7 @@
  *                      uses them, :1212-1272 _nfndh / _fill_dnfl
  *   pmi_cluster_*      picasso/clusterer.py:114-201 _cluster (the SMLM clusterer),
  *                      :34-111 _frame_analysis / frame_analysis, :410-445 _dbscan
+ *   pmi_centers_*      picasso/clusterer.py:694-897 find_cluster_centers and its helpers
  *   pmi_pairs_*        picasso/postprocess.py:37-94 get_index_blocks, :169-204
  *                      _fill_index_blocks, :1543-1579 _local_density (:1582-1631
  *                      compute_local_density), :960-999 _distance_histogram
@@ -575,6 +576,60 @@ int pmi_pairs_density_dev(const void *d_x, int x_type, const void *d_y, int y_ty
 int pmi_pairs_distance_hist_dev(const void *d_x, int x_type, const void *d_y, int y_type, const int32_t *d_rows,
                                 const uint64_t *d_keys, int64_t n, int64_t p, int64_t K, int64_t L, double r_max,
                                 double r2, double bin_size, int64_t n_bins, uint64_t *d_hist, void *stream);
+
+/* ---- cluster centers (picasso/clusterer.py:694-897 find_cluster_centers, csrc/centers.hip) --------------------- *
+ * The per-cluster statistics of a table with a `group` column.  d_group is int64 (the host widens any integer column),
+ * g_min / g_max its smallest and largest value (they size the sort: keys are group - g_min, so negative labels come
+ * first).  Columns are device arrays IN THE CALLER'S ROW ORDER, of the type named beside them.  At most 2^31 - 2 rows.
+ * Scratch comes from the library's arena; every call runs on `stream` and synchronises it before it returns.
+ *
+ * pmi_centers_order_dev    d_rows[q] (int32, n entries) = the row at sorted position q, equal to
+ *                          np.argsort(group, kind="stable"); d_unique[g] (int64, room for n) = the distinct labels,
+ *                          ascending; d_start[g] (int32, room for n + 1) = the first sorted position of label g, with
+ *                          d_start[*n_groups] = n.
+ * pmi_centers_weights_dev  d_w[i] = 1 / (lpx[i] + lpy[i])^2 in the columns' type (PMI_CENTERS_F32 / _F64), per row.
+ * pmi_centers_stats_dev    per column descriptor, one sequential chain per label over its rows in sorted order (which is
+ *                          table order within a label), as pandas' group_mean / group_sum / group_var run them:
+ *                            PMI_CENTERS_MEAN    sum / mean: Kahan-compensated sum of the values that are not NaN, in
+ *                                                float32 for a float32 column and in float64 (of the converted value)
+ *                                                for every other; the compensation is reset to 0 when it becomes NaN;
+ *                                                mean = sum / count of those values in the same type, NaN for none.
+ *                                                std: Welford's update in float64 for every type, ddof 1, square root in
+ *                                                float64, NaN for fewer than two values.  sum / mean / std are written
+ *                                                where the pointer is not NULL (sum and mean in the summing type, std
+ *                                                float64).
+ *                            PMI_CENTERS_XSUM    the same sum of data[i] * weight[i], float64 unless both are float32
+ *                                                (float columns only).
+ *                            PMI_CENTERS_FIRST   sum[g] = the label's first value that is not NaN (NaN where there is
+ *                                                none), in the column's own type.
+ *                            PMI_CENTERS_EVENTS  sum[g] (int32) = the sorted positions of the label that are its first
+ *                                                or whose frame - previous frame > 3, the difference taken in the
+ *                                                integer column's own type (an unsigned column that decreases wraps
+ *                                                and counts).
+ *                          At most 32 descriptors.
+ * pmi_centers_hull_dev     d_area[g] (float64) = the area of the convex hull of the label's (x, y) as float64: rows are
+ *                          ordered by (label, x, y) with three stable radix sorts, one lane per label runs the monotone
+ *                          chain and sums the shoelace terms relative to the first hull vertex.  0.0 for fewer than three
+ *                          hull vertices or collinear rows.  x / y float32 or float64, each on its own. */
+enum pmi_centers_type { PMI_CENTERS_F32 = 0, PMI_CENTERS_F64 = 1, PMI_CENTERS_U32 = 2, PMI_CENTERS_I32 = 3,
+                        PMI_CENTERS_U64 = 4, PMI_CENTERS_I64 = 5 };
+enum pmi_centers_op { PMI_CENTERS_MEAN = 0, PMI_CENTERS_XSUM = 1, PMI_CENTERS_FIRST = 2, PMI_CENTERS_EVENTS = 3 };
+typedef struct pmi_centers_column {
+    const void *data;     /* device column */
+    const void *weight;   /* device column (XSUM) */
+    void *sum;            /* device, n_groups entries; may be NULL for MEAN */
+    void *mean;           /* device, n_groups entries (MEAN), may be NULL */
+    void *std;            /* device, n_groups float64 entries (MEAN), may be NULL */
+    int32_t op, type, w_type;
+} pmi_centers_column;
+int pmi_centers_order_dev(const int64_t *d_group, int64_t n, int64_t g_min, int64_t g_max, int32_t *d_rows,
+                          int32_t *d_start, int64_t *d_unique, int64_t *n_groups, void *stream);
+int pmi_centers_weights_dev(const void *d_lpx, const void *d_lpy, int type, int64_t n, void *d_w, void *stream);
+int pmi_centers_stats_dev(const int32_t *d_rows, const int32_t *d_start, int64_t n, int64_t n_groups,
+                          const pmi_centers_column *columns, int n_columns, void *stream);
+int pmi_centers_hull_dev(const void *d_x, int x_type, const void *d_y, int y_type, const int64_t *d_group,
+                         int64_t g_min, int64_t g_max, const int32_t *d_start, int64_t n, int64_t n_groups,
+                         double *d_area, void *stream);
 
 /* ---- timing hooks for bench.py (HIP events on the given stream) ------- */
 int pmi_event_create(void **event);

@@ -971,3 +971,149 @@ class BlockTable:
                 float(r_max), float(r2), float(bin_size), int(n_bins), _dptr(hist), ctypes.c_void_p(self.stream)),
                 "pmi_pairs_distance_hist_dev")
             return hist[:int(n_bins)].cpu().numpy().view(np.uint64)
+
+
+# ---- cluster centers (csrc/centers.hip, picasso/clusterer.py:694-897) ----
+CENTERS_MEAN, CENTERS_XSUM, CENTERS_FIRST, CENTERS_EVENTS = 0, 1, 2, 3
+_CENTERS_TYPES = {np.dtype("float32"): 0, np.dtype("float64"): 1, np.dtype("uint32"): 2, np.dtype("int32"): 3,
+                  np.dtype("uint64"): 4, np.dtype("int64"): 5}
+
+
+class _CentersColumn(ctypes.Structure):
+    _fields_ = [("data", ctypes.c_void_p), ("weight", ctypes.c_void_p), ("sum", ctypes.c_void_p),
+                ("mean", ctypes.c_void_p), ("std", ctypes.c_void_p),
+                ("op", ctypes.c_int32), ("type", ctypes.c_int32), ("w_type", ctypes.c_int32)]
+
+
+def centers_type(dtype, floating: bool = False) -> int:
+    dt = np.dtype(dtype)
+    if dt not in _CENTERS_TYPES or (floating and dt.kind != "f"):
+        raise TypeError(f"unsupported column dtype {dt} for the cluster centers on the device")
+    return _CENTERS_TYPES[dt]
+
+
+def _centers_column(a, what: str) -> np.ndarray:
+    """A table column as the device takes it: bool and the narrow integers widened (to a type pandas would convert
+    to float64 all the same), float16 refused."""
+    a = np.asarray(a)
+    if a.dtype.kind == "b" or (a.dtype.kind in "iu" and a.dtype.itemsize < 4):
+        a = a.astype(np.int32 if a.dtype.kind != "u" else np.uint32)
+    if a.ndim != 1:
+        raise ValueError(f"{what} must be a column, not an array of shape {a.shape}")
+    centers_type(a.dtype)
+    return a
+
+
+class CenterGroups:
+    """The rows of a table in the order of their ``group`` column, sent to the device once (pmi_centers_order_dev):
+    ``unique`` are the distinct labels ascending (what ``groupby(sort=True)`` returns), ``n_locs`` their sizes,
+    ``order()`` is ``np.argsort(group, kind="stable")``.  Every statistic is one array per distinct label."""
+
+    def __init__(self, group):
+        import torch
+        _lib.require_gpu()
+        group = _index_column(group, "group")
+        if group.ndim != 1 or len(group) == 0:
+            raise ValueError("group must be a column of at least one row")
+        self.n = int(len(group))
+        self.g_min, self.g_max = int(group.min()), int(group.max())
+        self.group = _to_device(group)
+        self.device = self.group.device
+        self.stream = torch.cuda.current_stream(self.device).cuda_stream
+        self.rows = torch.empty(self.n, dtype=torch.int32, device=self.device)
+        self.start = torch.empty(self.n + 1, dtype=torch.int32, device=self.device)
+        unique = torch.empty(self.n, dtype=torch.int64, device=self.device)
+        G = ctypes.c_int64(0)
+        with _lib.lock():
+            _lib.check(_lib.load().pmi_centers_order_dev(
+                _dptr(self.group), self.n, self.g_min, self.g_max, _dptr(self.rows), _dptr(self.start), _dptr(unique),
+                ctypes.byref(G), ctypes.c_void_p(self.stream)), "pmi_centers_order_dev")
+            self.n_groups = int(G.value)
+            self.unique = unique[:self.n_groups].cpu().numpy()
+            self.offsets = self.start[:self.n_groups + 1].cpu().numpy()
+        self.n_locs = np.diff(self.offsets).astype(np.int64)
+        self._cache = {}
+
+    def order(self) -> np.ndarray:
+        """The int64 stable permutation into group order."""
+        return self.rows.cpu().numpy().astype(np.int64)
+
+    def _dev(self, a):
+        """One upload per host column, however many statistics read it."""
+        key = (a.__array_interface__["data"][0], a.strides, a.dtype.str)      # two views of one column are one upload
+        if key not in self._cache:
+            if len(a) != self.n:
+                raise ValueError("every column must have one entry per row of the table")
+            self._cache[key] = (a, _to_device(a))
+        return self._cache[key][1]
+
+    def weights(self, lpx, lpy):
+        """Device column ``1.0 / (lpx + lpy) ** 2`` in NumPy's result type of the two -> (tensor, dtype)."""
+        import torch
+        lpx, lpy = np.asarray(lpx), np.asarray(lpy)
+        dt = np.result_type(lpx.dtype, lpy.dtype)
+        code = centers_type(dt, True)
+        d_x, d_y = _to_device(lpx, dt), _to_device(lpy, dt)
+        if len(lpx) != self.n or len(lpy) != self.n:
+            raise ValueError("every column must have one entry per row of the table")
+        w = torch.empty(self.n, dtype=torch.float32 if code == 0 else torch.float64, device=self.device)
+        with _lib.lock():
+            _lib.check(_lib.load().pmi_centers_weights_dev(_dptr(d_x), _dptr(d_y), code, self.n, _dptr(w),
+                                                           ctypes.c_void_p(self.stream)), "pmi_centers_weights_dev")
+        return w, np.dtype(dt)
+
+    def stats(self, requests):
+        """``requests``: a list of (op, column, weight, wants) with ``wants`` a subset of ("sum", "mean", "std") for
+        CENTERS_MEAN and ignored otherwise; ``column`` a host column or the (tensor, dtype) of ``weights()``, which
+        is also what ``weight`` takes.
+        -> one dict of arrays per request ("sum" holds the result of the other ops)."""
+        import torch
+        G = self.n_groups
+        desc = (_CentersColumn * max(len(requests), 1))()
+        keep, outs = [], []
+        for i, (op, column, weight, wants) in enumerate(requests):
+            if isinstance(column, tuple):                   # already on the device: what weights() returned
+                d, dtype = column
+            else:
+                column = _centers_column(column, "a statistics column")
+                d, dtype = self._dev(column), column.dtype
+            code = centers_type(dtype, op == CENTERS_XSUM)
+            w_code, w_ptr = 0, None
+            if op == CENTERS_MEAN:
+                acc = np.dtype(np.float32) if code == 0 else np.dtype(np.float64)
+                types = {"sum": acc, "mean": acc, "std": np.dtype(np.float64)}
+                wants = tuple(wants)
+            elif op == CENTERS_XSUM:
+                w_t, w_dt = weight
+                w_code, w_ptr = centers_type(w_dt, True), w_t.data_ptr()
+                keep.append(w_t)
+                types, wants = {"sum": np.promote_types(dtype, w_dt)}, ("sum",)
+            elif op == CENTERS_FIRST:
+                types, wants = {"sum": np.dtype(dtype)}, ("sum",)
+            elif op == CENTERS_EVENTS:
+                types, wants = {"sum": np.dtype(np.int32)}, ("sum",)
+            else:
+                raise ValueError(f"unknown statistics op {op}")
+            out = {k: _to_device(np.zeros(G, types[k])) for k in wants}
+            outs.append((out, types))
+            keep.append(d)
+            desc[i] = _CentersColumn(d.data_ptr(), w_ptr, *(out[k].data_ptr() if k in out else None
+                                                             for k in ("sum", "mean", "std")), int(op), code, w_code)
+        with _lib.lock():
+            _lib.check(_lib.load().pmi_centers_stats_dev(
+                _dptr(self.rows), _dptr(self.start), self.n, G, ctypes.cast(desc, ctypes.c_void_p), len(requests),
+                ctypes.c_void_p(self.stream)), "pmi_centers_stats_dev")
+            return [{k: t.cpu().numpy().view(types[k]) for k, t in out.items()} for out, types in outs]
+
+    def hull_areas(self, x, y) -> np.ndarray:
+        """float64 area of the convex hull of every label's (x, y)."""
+        import torch
+        x, y = np.asarray(x), np.asarray(y)
+        tx, ty = centers_type(x.dtype, True), centers_type(y.dtype, True)
+        d_x, d_y = self._dev(x), self._dev(y)
+        area = torch.zeros(self.n_groups, dtype=torch.float64, device=self.device)
+        with _lib.lock():
+            _lib.check(_lib.load().pmi_centers_hull_dev(
+                _dptr(d_x), tx, _dptr(d_y), ty, _dptr(self.group), self.g_min, self.g_max, _dptr(self.start), self.n,
+                self.n_groups, _dptr(area), ctypes.c_void_p(self.stream)), "pmi_centers_hull_dev")
+            return area.cpu().numpy()

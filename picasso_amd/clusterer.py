@@ -1,17 +1,21 @@
-"""DBSCAN and the SMLM clusterer of picasso.clusterer (picasso/clusterer.py:34-544, :665-691) on top of
-csrc/cluster.hip: the same signatures, defaults, warnings, errors, dtypes, ``info`` entries and column handling,
-and the same int32 label for every row.
+"""DBSCAN, the SMLM clusterer and the cluster centers of picasso.clusterer (picasso/clusterer.py:34-544, :665-897)
+on top of csrc/cluster.hip and csrc/centers.hip: the same signatures, defaults, warnings, errors, dtypes, ``info``
+entries and column handling, the same int32 label for every row and the same table of centers.
 
 The table handling stays the reference's own NumPy / pandas calls on the same dtypes (``z /= pixelsize`` on the
 float32 column, the float32 ``X[:, 2] *= radius_xy / radius_z``, the widening to float64 that its KDTree and
 sklearn do); the neighbour search, the local maxima, the union of core rows, the label sizes and the frame
-analysis run on the device.  ``hdbscan``, ``find_cluster_centers``, ``cluster_areas`` and ``test_subclustering``
-are not here: they stay the reference's and work on the tables these functions return.
+analysis run on the device.  ``find_cluster_centers`` computes every per-cluster quantity on the device in pandas'
+own arithmetic (the group order, the Kahan means and sums, the Welford standard deviations, the binding events,
+``first()`` and the 2-D hull area); the derived columns are the reference's NumPy lines on those arrays, and the
+volume of a 3-D hull stays its per-cluster scipy call on the host.  ``hdbscan``, ``cluster_areas`` and
+``test_subclustering`` are not here: they stay the reference's and work on the tables these functions return.
 
 Edges, as the reference has them: an empty table gives empty labels from ``_cluster`` (and a ``ValueError`` from
 the frame analysis, which takes the maximum of no frames), a ``ValueError`` from ``_dbscan`` (sklearn wants one
 sample) and a ``ZeroDivisionError`` from ``cluster`` / ``dbscan``; coordinates that are not finite raise
-``ValueError`` (scipy's KDTree and sklearn both refuse them).
+``ValueError`` (scipy's KDTree and sklearn both refuse them).  ``find_cluster_centers`` raises the reference's
+``IndexError`` on an empty table and scipy's ``ValueError`` on a NaN coordinate.
 """
 from __future__ import annotations
 
@@ -22,7 +26,8 @@ from . import __version__, backend, lib
 
 # what localize.install() rebinds on picasso.clusterer
 CLUSTERER_NAMES = ("_frame_analysis", "frame_analysis", "_cluster", "cluster_2D", "cluster_3D", "cluster", "_dbscan",
-                   "dbscan", "extract_valid_labels")
+                   "dbscan", "extract_valid_labels", "_count_binding_events", "_cluster_convex_hulls",
+                   "_weighted_z_means", "find_cluster_centers")
 _FA_BINS = 20
 
 
@@ -197,3 +202,158 @@ def extract_valid_labels(locs: pd.DataFrame, labels: np.ndarray) -> pd.DataFrame
     (clusterer.py:665-691)."""
     locs["group"] = labels
     return locs[locs["group"] != -1]
+
+
+# ---- cluster centers (clusterer.py:694-897) ----
+_MEAN_COLS = ("frame", "x", "y", "photons", "sx", "sy", "bg", "net_gradient")
+_STD_COLS = ("frame", "x", "y")
+
+
+def _groups(group_arr) -> "backend.CenterGroups":
+    if len(group_arr) == 0:
+        # new_event[0] = True of _count_binding_events (clusterer.py:750)
+        raise IndexError("index 0 is out of bounds for axis 0 with size 0")
+    return backend.CenterGroups(group_arr)
+
+
+def _events_column(frame_arr) -> np.ndarray:
+    frame_arr = np.asarray(frame_arr)
+    if frame_arr.dtype.kind not in "iu" or frame_arr.dtype.itemsize < 4:
+        raise TypeError(f"frame must be a 32- or 64-bit integer column, not {frame_arr.dtype}")
+    return frame_arr
+
+
+def _count_binding_events(group_arr, frame_arr, groups=None):
+    """Binding events per cluster (clusterer.py:728-757): a new event starts where consecutive frames of a cluster,
+    in table order, are more than 3 apart in the frame column's own type.
+    -> (n_events per sorted unique group, the stable argsort by group, ``group_arr`` in that order)."""
+    groups = groups or _groups(group_arr)
+    n_events = groups.stats([(backend.CENTERS_EVENTS, _events_column(frame_arr), None, ())])[0]["sum"]
+    order = groups.order()
+    return n_events.astype(np.int64), order, np.asarray(group_arr)[order]
+
+
+def _hull_volumes(locs, order, group_s, unique_groups, pixelsize) -> np.ndarray:
+    """The volume of every cluster's 3-D hull: the reference's scipy call per cluster on slices of the device's group
+    order (clusterer.py:773-788)."""
+    from scipy.spatial import ConvexHull, QhullError
+    coords_sorted = locs[["x", "y", "z"]].to_numpy()[order].astype(np.float64, copy=True)
+    coords_sorted[:, 2] /= pixelsize
+    group_offsets = np.searchsorted(group_s, unique_groups, side="left")
+    group_offsets = np.append(group_offsets, len(group_s))
+    convexhull = np.zeros(len(unique_groups), dtype=np.float64)
+    for i in range(len(unique_groups)):
+        X = coords_sorted[group_offsets[i]: group_offsets[i + 1]]
+        try:
+            convexhull[i] = ConvexHull(X).volume
+        except QhullError:
+            convexhull[i] = 0.0
+    return convexhull
+
+
+def _cluster_convex_hulls(locs: pd.DataFrame, order, group_s, unique_groups, has_z: bool, pixelsize, groups=None):
+    """Convex-hull area (2-D, on the device) or volume (3-D, scipy per cluster) of every cluster
+    (clusterer.py:760-788).  0.0 where the rows span no area: one or two rows, duplicates, collinear rows."""
+    if has_z:
+        return _hull_volumes(locs, order, group_s, unique_groups, pixelsize)
+    x, y = locs["x"].to_numpy(), locs["y"].to_numpy()
+    if np.isnan(x).any() or np.isnan(y).any():
+        raise ValueError("Points cannot contain NaN")           # scipy's, from the first cluster that holds one
+    groups = groups or _groups(locs["group"].to_numpy())
+    return groups.hull_areas(x, y)
+
+
+def _weighted_z_means(locs: pd.DataFrame, group_arr, groups=None) -> np.ndarray:
+    """Per-cluster z mean weighted by 1 / (lpx + lpy)^2 (clusterer.py:791-800)."""
+    groups = groups or _groups(group_arr)
+    w = groups.weights(locs["lpx"].to_numpy(), locs["lpy"].to_numpy())
+    ws, wz = groups.stats([(backend.CENTERS_MEAN, w, None, ("sum",)),
+                           (backend.CENTERS_XSUM, locs["z"].to_numpy(), w, ())])
+    return (pd.Series(wz["sum"]) / pd.Series(ws["sum"])).to_numpy()
+
+
+def find_cluster_centers(locs: pd.DataFrame, pixelsize: float | None = None) -> pd.DataFrame:
+    """Cluster centers of a table with a ``group`` column (clusterer.py:803-897): one row per cluster in the format
+    of localizations, the same columns, dtypes and values as the reference's.  ``pixelsize`` is needed for 3-D."""
+    has_z = "z" in locs.columns
+    if has_z and pixelsize is None:
+        raise ValueError(
+            "Camera pixel size must be specified as an integer for 3D"
+            " cluster centers calculation."
+        )
+    group_arr = locs["group"].to_numpy()
+    frame_arr = locs["frame"].to_numpy()
+    mean_cols = list(_MEAN_COLS) + (["z"] if has_z else [])
+    std_cols = list(_STD_COLS) + (["z"] if has_z else [])
+    columns = {c: locs[c].to_numpy() for c in mean_cols}
+    groups = _groups(group_arr)
+
+    requests = [(backend.CENTERS_MEAN, columns[c], None, ("mean", "std") if c in std_cols else ("mean",))
+                for c in mean_cols]
+    requests.append((backend.CENTERS_EVENTS, _events_column(frame_arr), None, ()))
+    if "group_input" in locs.columns:
+        requests.append((backend.CENTERS_FIRST, locs["group_input"].to_numpy(), None, ()))
+    res = groups.stats(requests)
+    s = {f"{c}_mean": r["mean"] for c, r in zip(mean_cols, res)}
+    # pandas returns the standard deviation of a float32 column as float32
+    s.update({f"{c}_std": r["std"].astype(np.float32) if columns[c].dtype == np.float32 else r["std"]
+              for c, r in zip(mean_cols, res) if c in std_cols})
+    s["n_locs"] = groups.n_locs
+    s["unique_groups"] = groups.unique
+    n_events = res[len(mean_cols)]["sum"]
+
+    lpx = s["x_std"] / np.sqrt(s["n_locs"])
+    lpy = s["y_std"] / np.sqrt(s["n_locs"])
+    ellipticity = s["sx_mean"] / s["sy_mean"]
+    if has_z:
+        order = groups.order()
+        convexhull = _cluster_convex_hulls(locs, order, group_arr[order], s["unique_groups"], has_z, pixelsize)
+    else:
+        convexhull = _cluster_convex_hulls(locs, None, None, s["unique_groups"], has_z, pixelsize, groups)
+
+    columns = {
+        "frame": s["frame_mean"].astype(np.float32),
+        "std_frame": s["frame_std"].astype(np.float32),
+        "x": s["x_mean"].astype(np.float32),
+        "y": s["y_mean"].astype(np.float32),
+        "std_x": s["x_std"].astype(np.float32),
+        "std_y": s["y_std"].astype(np.float32),
+    }
+    if has_z:
+        columns["z"] = _weighted_z_means(locs, group_arr, groups).astype(np.float32)
+    columns.update(
+        {
+            "photons": s["photons_mean"].astype(np.float32),
+            "sx": s["sx_mean"].astype(np.float32),
+            "sy": s["sy_mean"].astype(np.float32),
+            "bg": s["bg_mean"].astype(np.float32),
+            "lpx": lpx.astype(np.float32),
+            "lpy": lpy.astype(np.float32),
+        }
+    )
+    if has_z:
+        columns["lpz"] = (s["z_std"] / np.sqrt(s["n_locs"])).astype(np.float32)
+        columns["std_z"] = s["z_std"].astype(np.float32)
+    columns.update(
+        {
+            "ellipticity": ellipticity.astype(np.float32),
+            "net_gradient": s["net_gradient_mean"].astype(np.float32),
+            "n_locs": s["n_locs"].astype(np.uint32),
+            "n_events": n_events.astype(np.int32),
+        }
+    )
+    if has_z:
+        volume = (
+            np.power((s["x_std"] + s["y_std"] + s["z_std"] / pixelsize) / 3 * 2, 3)
+            * 4.18879
+        )  # assume radius = 2 * std_xyz
+        columns["volume"] = volume.astype(np.float32)
+    else:
+        # assume radius = 2 * std_xy
+        area = np.power(s["x_std"] + s["y_std"], 2) * np.pi
+        columns["area"] = area.astype(np.float32)
+    columns["convexhull"] = convexhull.astype(np.float32)
+    columns["group"] = s["unique_groups"].astype(np.int32)
+    if "group_input" in locs.columns:
+        columns["group_input"] = res[len(mean_cols) + 1]["sum"].astype(np.int32)
+    return pd.DataFrame(columns)

@@ -840,7 +840,8 @@ def install(picasso_localize=None, picasso_gaussmle=None, picasso_gausslq=None, 
     (``postprocess.LINK_NENA_NAMES``), and ``picasso.localize`` the two quick checks built on them, ``check_nena`` and
     ``check_kinetics``, and the local density, distance histogram and pair correlation (``postprocess.PAIR_NAMES``).
     ``picasso_clusterer`` (default: ``picasso.clusterer`` when it imports) gets DBSCAN, the SMLM
-    clusterer and the frame analysis (``clusterer.CLUSTERER_NAMES``); HDBSCAN and the cluster statistics stay its own."""
+    clusterer, the frame analysis and the cluster centers, ``find_cluster_centers`` with the helpers under it
+    (``clusterer.CLUSTERER_NAMES``); HDBSCAN, ``cluster_areas`` and ``test_subclustering`` stay its own."""
     if picasso_localize is None:
         import picasso.localize as picasso_localize       # the installed reference
     if picasso_gaussmle is None:
