@@ -16,7 +16,9 @@
 //   3. one workgroup per tile: 256 threads x 4 pixels in registers; the tile's list is walked
 //      in chunks of 32 localizations whose 1-D profiles (float64 exp, rounded to float32 like
 //      the reference's gx / gy arrays) are built cooperatively in LDS, then every pixel adds
-//      gy*gx of each localization in order (0 outside the footprint: x + 0 == x).
+//      gy*gx of each localization in order.  The profiles are 0 outside the footprint and
+//      x + 0 == x, so a localization with finite profiles is added to the whole tile unmasked; one
+//      with an inf or NaN profile value (inf * 0 = NaN) is added inside its footprint only.
 // The result is the reference's image bit for bit, up to a 1-ulp difference between the
 // device's and glibc's float64 exp surviving the rounding to float32.
 #include <algorithm>
@@ -148,6 +150,8 @@ __global__ __launch_bounds__(256) void tile_kernel(const Loc *__restrict__ locs,
                                                    View v, float *__restrict__ image)
 {
     __shared__ float s_gx[CHUNK][TILE], s_gy[CHUNK][TILE];
+    __shared__ unsigned s_fp[CHUNK];     // footprint in tile coordinates, one byte each: col min, col max, row min, row max
+    __shared__ unsigned s_bad[2];        // bit l: localization l of the chunk has a non-finite profile value (even / odd chunks)
     const int tile = blockIdx.x;
     const unsigned e0 = start[tile], e1 = end[tile];
     const int ty = tile / v.tiles_x, tx = tile - ty * v.tiles_x;
@@ -155,7 +159,10 @@ __global__ __launch_bounds__(256) void tile_kernel(const Loc *__restrict__ locs,
     const int tid = threadIdx.x;
     const int pj = tid & (TILE - 1), pi = tid >> 5;           // pixel (pi + 8 k, pj), k = 0..3
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
-    for (unsigned c0 = e0; c0 < e1; c0 += CHUNK) {
+    if (tid < 2) s_bad[tid] = 0;
+    __syncthreads();
+    int par = 0;
+    for (unsigned c0 = e0; c0 < e1; c0 += CHUNK, par ^= 1) {
         const int nloc = (int)min((unsigned)CHUNK, e1 - c0);
         // profiles: 2 * TILE values per localization, CHUNK localizations -> 8 values per thread
         for (int q = tid; q < CHUNK * 2 * TILE; q += 256) {
@@ -179,14 +186,39 @@ __global__ __launch_bounds__(256) void tile_kernel(const Loc *__restrict__ locs,
                         val = (float)(norm * exp(-dy * dy * inv_2sy2));
                     }
                 }
+                if (!isfinite(val)) atomicOr(&s_bad[par], 1u << l);
+                if (r == 0)
+                    s_fp[l] = (unsigned)min(max(L.j_min - col0, 0), TILE) | (unsigned)min(max(L.j_max - col0, 0), TILE) << 8 |
+                              (unsigned)min(max(L.i_min - row0, 0), TILE) << 16 | (unsigned)min(max(L.i_max - row0, 0), TILE) << 24;
             }
             if (r < TILE) s_gx[l][r] = val; else s_gy[l][r - TILE] = val;
         }
         __syncthreads();
-        for (int l = 0; l < nloc; l++) {
-            const float gx = s_gx[l][pj];
+        const unsigned bad = __builtin_amdgcn_readfirstlane(s_bad[par]);      // the same in every wave of the tile
+        if (tid == 0) s_bad[par ^ 1] = 0;                                     // the next chunk's, last read before the barrier above
+        if (bad == 0) {
+            for (int l = 0; l < nloc; l++) {
+                const float gx = s_gx[l][pj];
 #pragma unroll
-            for (int k = 0; k < 4; k++) acc[k] = acc[k] + s_gy[l][pi + 8 * k] * gx;
+                for (int k = 0; k < 4; k++) acc[k] = acc[k] + s_gy[l][pi + 8 * k] * gx;
+            }
+        } else {
+            for (int l = 0; l < nloc; l++) {
+                const float gx = s_gx[l][pj];
+                if (!((bad >> l) & 1u)) {
+#pragma unroll
+                    for (int k = 0; k < 4; k++) acc[k] = acc[k] + s_gy[l][pi + 8 * k] * gx;
+                } else {                                         // inf * 0 would be NaN: leave every pixel outside the footprint alone
+                    const unsigned fp = s_fp[l];
+                    const bool in_col = pj >= (int)(fp & 255u) && pj < (int)((fp >> 8) & 255u);
+                    const int r_min = (int)((fp >> 16) & 255u), r_max = (int)(fp >> 24);
+#pragma unroll
+                    for (int k = 0; k < 4; k++) {
+                        const int row = pi + 8 * k;
+                        if (in_col && row >= r_min && row < r_max) acc[k] = acc[k] + s_gy[l][row] * gx;
+                    }
+                }
+            }
         }
         __syncthreads();
     }

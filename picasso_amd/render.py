@@ -4,6 +4,20 @@ widths = localization precisions) and ``"gaussian_iso"`` (one width, their mean)
 :798-853 ``_render_hist``, :1020-1070 ``_render_gaussian``; the pixels are computed by
 csrc/render.hip.  Rotated views (``ang``) and the other blur methods are not built; they
 raise instead of falling back to a CPU path.
+
+Zero blur width.  The reference draws each localization in ``_draw_gaussian_loc``, compiled by numba
+with Python's error model, so ``1.0 / (2.0 * sx_ * sx_)`` raises ``ZeroDivisionError`` when a
+localization that is drawn has a width of exactly 0.  The two layers split that as follows:
+
+* this module (``render``, ``_render_gaussian``, ``_render_gaussian_iso`` and the three older names)
+  raises ``ZeroDivisionError`` like the reference.  The widths are evaluated on the host columns as
+  the kernel evaluates them: in float32, after ``np.maximum`` with ``min_blur_width``, after the
+  multiplication by the oversampling and, for ``gaussian_iso``, after the mean.  Only rows in view
+  count, and only rows whose footprint is not empty: a NaN width has an empty footprint, the
+  reference returns before the division, nothing raises.
+* ``backend.render_arrays`` and the C ABI (``pmi_render_gaussian*``) keep IEEE semantics, like
+  ``oracle.render``: a zero width gives a NaN at the one pixel of its footprint and leaves every
+  other pixel as it was.
 """
 from __future__ import annotations
 
@@ -47,6 +61,39 @@ def render(locs: pd.DataFrame, info, oversampling: float = 1.0, viewport=None, b
     raise Exception("blur_method not understood.")
 
 
+def _int32(v):
+    """float64 -> int32 as the compiled reference does it (cvttsd2si): truncation, INT_MIN for NaN / out of range."""
+    ok = (v == v) & (v < 2147483648.0) & (v >= -2147483648.0)
+    return np.where(ok, np.trunc(np.where(ok, v, 0.0)), -2147483648.0).astype(np.int64)
+
+
+def _raise_on_zero_width(x, y, lpx, lpy, oversampling, y_min, x_min, y_max, x_max, min_blur_width, iso):
+    """ZeroDivisionError where the reference's ``_draw_gaussian_loc`` divides by a zero width (module docstring)."""
+    x = np.asarray(x, np.float32).astype(np.float64)
+    y = np.asarray(y, np.float32).astype(np.float64)
+    osf, mbw = np.float32(oversampling), np.float32(min_blur_width)
+    with np.errstate(all="ignore"):
+        sx = osf * np.maximum(np.asarray(lpx, np.float32), mbw)
+        sy = osf * np.maximum(np.asarray(lpy, np.float32), mbw)
+        if iso:
+            sy = (sy + sx) / np.float32(2.0)
+            sx = sy
+        rows = np.flatnonzero(((sx == 0) | (sy == 0)) & (x > x_min) & (y > y_min) & (x < x_max) & (y < y_max))
+        if len(rows) == 0:
+            return
+        # the division is reached only behind the reference's "nx <= 0 or ny <= 0: return" (render.py:505-524)
+        n_y = int(np.ceil(oversampling * (y_max - y_min)))
+        n_x = int(np.ceil(oversampling * (x_max - x_min)))
+        x_ = oversampling * (x[rows] - x_min)
+        y_ = oversampling * (y[rows] - y_min)
+        oy = 3.0 * sy[rows].astype(np.float64)
+        ox = 3.0 * sx[rows].astype(np.float64)
+        cy = np.minimum(_int32(y_ + oy + 1), n_y) - np.maximum(_int32(y_ - oy), 0)
+        cx = np.minimum(_int32(x_ + ox) + 1, n_x) - np.maximum(_int32(x_ - ox), 0)
+    if np.any((cx > 0) & (cy > 0)):
+        raise ZeroDivisionError("division by zero")
+
+
 def _render_hist(locs, oversampling, y_min, x_min, y_max, x_max, ang=None):
     if ang is not None:
         raise NotImplementedError("rotated rendering (ang) has no HIP kernel in picasso_amd")
@@ -56,17 +103,20 @@ def _render_hist(locs, oversampling, y_min, x_min, y_max, x_max, ang=None):
 def _render_gaussian(locs, oversampling, y_min, x_min, y_max, x_max, min_blur_width, ang=None):
     if ang is not None:
         raise NotImplementedError("rotated rendering (ang) has no HIP kernel in picasso_amd")
-    return backend.render_arrays(locs["x"].to_numpy(), locs["y"].to_numpy(), oversampling, y_min, x_min, y_max, x_max,
-                                 lpx=locs["lpx"].to_numpy(), lpy=locs["lpy"].to_numpy(), min_blur_width=min_blur_width)
+    x, y, lpx, lpy = (locs[c].to_numpy() for c in ("x", "y", "lpx", "lpy"))
+    _raise_on_zero_width(x, y, lpx, lpy, oversampling, y_min, x_min, y_max, x_max, min_blur_width, False)
+    return backend.render_arrays(x, y, oversampling, y_min, x_min, y_max, x_max, lpx=lpx, lpy=lpy,
+                                 min_blur_width=min_blur_width)
 
 
 def _render_gaussian_iso(locs, oversampling, y_min, x_min, y_max, x_max, min_blur_width, ang=None):
     """picasso/render.py:1148-1216: one isotropic width per localization, the mean of the two."""
     if ang is not None:
         raise NotImplementedError("rotated rendering (ang) has no HIP kernel in picasso_amd")
-    return backend.render_arrays(locs["x"].to_numpy(), locs["y"].to_numpy(), oversampling, y_min, x_min, y_max, x_max,
-                                 lpx=locs["lpx"].to_numpy(), lpy=locs["lpy"].to_numpy(), min_blur_width=min_blur_width,
-                                 iso=True)
+    x, y, lpx, lpy = (locs[c].to_numpy() for c in ("x", "y", "lpx", "lpy"))
+    _raise_on_zero_width(x, y, lpx, lpy, oversampling, y_min, x_min, y_max, x_max, min_blur_width, True)
+    return backend.render_arrays(x, y, oversampling, y_min, x_min, y_max, x_max, lpx=lpx, lpy=lpy,
+                                 min_blur_width=min_blur_width, iso=True)
 
 
 def _older_name(name: str) -> None:

@@ -567,3 +567,42 @@ def test_lq_chain_scratch_layouts_are_free_of_bank_conflicts():
         if w <= 9:
             assert wr_extra == 0, (w, wr_extra)
         assert 6 * s <= g or w == 7          # the columns of a spot fit its share (7x7: its own offsets, 262 + 50 = 312)
+
+
+def test_render_zero_width_check():
+    """render._raise_on_zero_width: ZeroDivisionError where the reference's _draw_gaussian_loc divides by a zero width
+    (picasso/render.py:521-525), with the widths evaluated in float32 as the kernel evaluates them."""
+    from picasso_amd import render
+    f = lambda *v: np.array(v, np.float32)      # noqa: E731
+    view = (0.0, 0.0, 64.0, 64.0)
+    ok = f(0.2, 0.3)
+    render._raise_on_zero_width(f(10.3, 20.0), f(10.7, 20.0), ok, ok, 1.0, *view, 0.0, False)
+    for lpx, lpy in ((f(0.2, 0.0), ok), (ok, f(0.0, 0.2))):
+        for iso in (False, True):
+            if iso and not (lpx[1] == 0 and lpy[1] == 0):
+                render._raise_on_zero_width(f(10.3, 20.0), f(10.7, 20.0), lpx, lpy, 1.0, *view, 0.0, iso)   # the mean is not 0
+                continue
+            with pytest.raises(ZeroDivisionError):
+                render._raise_on_zero_width(f(10.3, 20.0), f(10.7, 20.0), lpx, lpy, 1.0, *view, 0.0, iso)
+    zero = f(0.2, 0.0)
+    with pytest.raises(ZeroDivisionError):
+        render._raise_on_zero_width(f(10.3, 20.0), f(10.7, 20.0), zero, zero, 1.0, *view, 0.0, True)
+    # out of view, on the border (strict inequalities), or lifted by min_blur_width: nothing is divided
+    render._raise_on_zero_width(f(10.3, 70.0), f(10.7, 20.0), zero, zero, 1.0, *view, 0.0, False)
+    render._raise_on_zero_width(f(10.3, 64.0), f(10.7, 20.0), zero, zero, 1.0, *view, 0.0, False)
+    render._raise_on_zero_width(f(10.3, 20.0), f(10.7, 20.0), zero, zero, 1.0, *view, 0.01, False)
+    # float32(1e-20) * float32(1e-30) underflows to 0; float32(1e-10) * float32(1e-30) = 1e-40 is a subnormal, not 0
+    with pytest.raises(ZeroDivisionError):
+        render._raise_on_zero_width(f(10.3), f(10.7), f(1e-30), f(0.2), 1e-20, 0.0, 0.0, 1e22, 1e22, 0.0, False)
+    render._raise_on_zero_width(f(10.3), f(10.7), f(1e-30), f(0.2), 1e-10, 0.0, 0.0, 1e12, 1e12, 0.0, False)
+    # an empty footprint returns before the division: NaN or inf beside the zero width
+    for other in (np.nan, np.inf):
+        render._raise_on_zero_width(f(10.3), f(10.7), f(0.0), f(other), 1.0, *view, 0.0, False)
+        render._raise_on_zero_width(f(10.3), f(10.7), f(other), f(0.0), 1.0, *view, 0.0, False)
+    # np.maximum with min_blur_width = 0 turns every negative width into 0; below a negative min_blur_width it survives
+    with pytest.raises(ZeroDivisionError):
+        render._raise_on_zero_width(f(10.3), f(10.7), f(0.2), f(-np.inf), 1.0, *view, 0.0, False)
+    render._raise_on_zero_width(f(10.3), f(10.7), f(0.0), f(-np.inf), 1.0, *view, -1.0, False)      # empty
+    render._raise_on_zero_width(f(10.3), f(10.7), f(0.0), f(-0.3), 1.0, *view, -1.0, False)         # empty
+    with pytest.raises(ZeroDivisionError):
+        render._raise_on_zero_width(f(10.3), f(10.7), f(0.0), f(-0.1), 1.0, *view, -1.0, False)     # one pixel

@@ -284,6 +284,96 @@ def test_render_against_goldens(case):
     assert np.max(np.abs(iso - g[case + "_iso_numpy"])) < 2e-4 * max(1.0, float(g[case + "_iso_numpy"].max()))
 
 
+def _int32(v):
+    """float64 -> int32 of the compiled reference (cvttsd2si): truncation, INT_MIN for NaN / out of range."""
+    return int(v) if v == v and -2147483648.0 <= v < 2147483648.0 else -2147483648
+
+
+def _draw_gaussian_numpy(image, x_, y_, sx_, sy_):
+    """picasso/render.py:494-540 _draw_gaussian_loc in plain numpy: float64 arithmetic on the float64 coordinates and
+    the float32 widths, profiles rounded to float32, outer product and accumulation in float32.  IEEE division."""
+    n_y, n_x = image.shape
+    sx_, sy_ = float(sx_), float(sy_)
+    i_min, i_max = max(_int32(y_ - 3.0 * sy_), 0), min(_int32(y_ + 3.0 * sy_ + 1), n_y)
+    j_min, j_max = max(_int32(x_ - 3.0 * sx_), 0), min(_int32(x_ + 3.0 * sx_) + 1, n_x)
+    if j_max - j_min <= 0 or i_max - i_min <= 0:
+        return
+    with np.errstate(all="ignore"):
+        inv_2sx2 = np.float64(1.0) / (2.0 * sx_ * sx_)
+        inv_2sy2 = np.float64(1.0) / (2.0 * sy_ * sy_)
+        norm = np.float64(1.0) / (2.0 * np.pi * sx_ * sy_)
+        dx = np.arange(j_min, j_max) + 0.5 - x_
+        dy = np.arange(i_min, i_max) + 0.5 - y_
+        gx = np.exp(-dx * dx * inv_2sx2).astype(np.float32)
+        gy = (norm * np.exp(-dy * dy * inv_2sy2)).astype(np.float32)
+        image[i_min:i_max, j_min:j_max] += gy[:, None] * gx[None, :]
+
+
+def _render_numpy(case, iso):
+    (y_min, x_min), (y_max, x_max) = case.viewport
+    osamp = case.oversampling
+    image = np.zeros((int(np.ceil(osamp * (y_max - y_min))), int(np.ceil(osamp * (x_max - x_min)))), np.float32)
+    with np.errstate(all="ignore"):
+        sx = np.float32(osamp) * np.maximum(case.lpx, np.float32(case.min_blur))
+        sy = np.float32(osamp) * np.maximum(case.lpy, np.float32(case.min_blur))
+        if iso:
+            sy = (sy + sx) / np.float32(2.0)
+            sx = sy
+    n = 0
+    for i in range(len(case.x)):
+        xd, yd = float(case.x[i]), float(case.y[i])
+        if xd > x_min and yd > y_min and xd < x_max and yd < y_max:
+            n += 1
+            _draw_gaussian_numpy(image, osamp * (xd - x_min), osamp * (yd - y_min), sx[i], sy[i])
+    return n, image
+
+
+@pytest.mark.parametrize("method", ["gaussian", "gaussian_iso"])
+@pytest.mark.parametrize("name", ["inf_rows", "with_zero_width", "mixed", "among_ordinary", "odd_widths", "odd_widths_min_blur", "odd_widths_negative_min_blur"])
+def test_render_nonfinite_profiles_vs_numpy_restatement(name, method):
+    """The oracle is the reference of tests/test_gpu_render_edges.py, so it is pinned on those tables: a profile value
+    that is inf or NaN reaches the pixels of its own footprint and no other."""
+    import render_edge_tables as T
+    min_blur = {"odd_widths": 0.0, "odd_widths_min_blur": 0.5, "odd_widths_negative_min_blur": -1.0}
+    case = T.odd_widths(min_blur[name]) if name in min_blur else T.NONFINITE[name]()
+    n, img = orc.render(case.x, case.y, case.oversampling, case.viewport, case.lpx, case.lpy, method, case.min_blur)
+    rn, ref = _render_numpy(case, method == "gaussian_iso")
+    assert n == rn and img.shape == ref.shape and img.dtype == np.float32
+    bad = sorted(map(tuple, np.argwhere(~np.isfinite(img)).tolist()))
+    assert bad == sorted(map(tuple, np.argwhere(~np.isfinite(ref)).tolist()))
+    assert np.array_equal(np.isnan(img), np.isnan(ref)) and np.array_equal(np.isposinf(img), np.isposinf(ref))
+    ok = np.isfinite(ref)
+    assert np.array_equal(img[ok].view(np.uint32), ref[ok].view(np.uint32))
+    if method == "gaussian":                 # (row, column), worked out by hand from the tables
+        if name == "inf_rows":
+            assert bad == [(12, 50), (20, 20)] and np.isposinf(img[20, 20]) and np.isposinf(img[12, 50])
+        if name == "with_zero_width":
+            assert bad == [(10, 10), (12, 50), (20, 20)] and np.isnan(img[10, 10])
+        if name == "mixed":
+            assert bad == [(20, 20), (20, 43), (20, 44), (20, 45), (40, 10), (50, 30)]
+            assert np.isnan(img[50, 30]) and np.isposinf(np.delete(img[np.isfinite(img) == 0], -1)).all()
+            assert img[19, 20] > 0 and img[21, 20] > 0 and np.isfinite(img[19:22:2, 20]).all()
+
+
+@pytest.mark.parametrize("method", ["gaussian", "gaussian_iso"])
+@pytest.mark.parametrize("interleaved", [False, True])
+@pytest.mark.parametrize("m", [31, 32, 33, 64, 65, 97])
+def test_render_chunk_tables_depend_on_order(m, interleaved, method):
+    """The chunk-seam tables of the GPU tier test the order of the additions only if that order changes the float32
+    sum: the oracle on the reversed table differs in bits where the footprints overlap."""
+    import render_edge_tables as T
+    assert T.CHUNK_SIZES == [31, 32, 33, 64, 65, 97]
+    case = T.chunk_seam(m, interleaved)
+    (y_min, x_min), (y_max, x_max) = case.viewport
+    tile = (case.x > 32) & (case.x < 64) & (case.y > 0) & (case.y < 32)
+    assert tile.sum() == m and (interleaved or len(case.x) == m)
+    fwd = orc.render(case.x, case.y, case.oversampling, case.viewport, case.lpx, case.lpy, method, case.min_blur)[1]
+    rev = orc.render(case.x[::-1], case.y[::-1], case.oversampling, case.viewport, case.lpx[::-1], case.lpy[::-1], method,
+                     case.min_blur)[1]
+    assert T.order_matters(fwd, rev)
+    assert np.allclose(fwd, rev, rtol=1e-5, atol=0)          # the same sum, in another order
+
+
 @pytest.mark.parametrize("tag,box", [("ng7", 7), ("ng5", 5), ("ng9", 9)])
 def test_oracle_net_gradient_standalone(tag, box):
     """orc_net_gradient against the reference's _net_gradient on single frames (local maxima plus positions whose
