@@ -54,6 +54,8 @@
  *   pmi_cluster_*      picasso/clusterer.py:114-201 _cluster (the SMLM clusterer),
  *                      :34-111 _frame_analysis / frame_analysis, :410-445 _dbscan
  *   pmi_centers_*      picasso/clusterer.py:694-897 find_cluster_centers and its helpers
+ *   pmi_kinetics_*     picasso/postprocess.py:1985-2004 _dark_times (:1920-1982 compute_dark_times,
+ *                      dark_times), :3580-3649 groupprops
  *   pmi_pairs_*        picasso/postprocess.py:37-94 get_index_blocks, :169-204
  *                      _fill_index_blocks, :1543-1579 _local_density (:1582-1631
  *                      compute_local_density), :960-999 _distance_histogram
@@ -630,6 +632,44 @@ int pmi_centers_stats_dev(const int32_t *d_rows, const int32_t *d_start, int64_t
 int pmi_centers_hull_dev(const void *d_x, int x_type, const void *d_y, int y_type, const int64_t *d_group,
                          int64_t g_min, int64_t g_max, const int32_t *d_start, int64_t n, int64_t n_groups,
                          double *d_area, void *stream);
+
+/* ---- dark times and group properties (picasso/postprocess.py:1985-2004 _dark_times, :3580-3649 groupprops,
+ * csrc/kinetics.hip) --------------------------------------------------------------------------------------------- *
+ * Columns are int64 device arrays IN THE CALLER'S ROW ORDER unless said otherwise (the host widens any integer column).
+ * At most 2^31 - 2 rows.  Scratch comes from the library's arena; every call runs on `stream` and synchronises it.
+ *
+ * pmi_kinetics_dark_order_dev   orders the rows by (group - g_min, last_frame - l_min) with two stable radix sorts;
+ *                               l_min / l_max and g_min / g_max are the smallest and largest value of the two columns.
+ *                               d_rows[q] (int32, n) = the row at sorted position q, d_last_sorted[q] (int64, n) its
+ *                               last frame, d_run[q] (int32, n) the number of its group's run, d_start[r] (int32, room
+ *                               for n + 1) the first sorted position of run r, closed by n.
+ * pmi_kinetics_dark_search_dev  d_dark[i] (int64, n) = the smallest frame[i] - last_frame[j] > 0 over the other rows j
+ *                               of row i's group, as a signed 64-bit difference, when it is < max_frame; -1 otherwise.
+ *                               One lane per sorted position bisects its own run.
+ * pmi_kinetics_stats_dev        per column descriptor and group (d_rows / d_start are pmi_centers_order_dev's: rows in
+ *                               table order within a group) what pandas' Series.mean() / Series.std() return, as
+ *                               float64: NaN counted as 0 and counted out; every sum is NumPy's add.reduce (an
+ *                               accumulator from 0 over the pairwise sums of 8192-element chunks).  mean: the sum in
+ *                               float32 for a float32 column and in float64 (of the converted value) for every other,
+ *                               over the count in that type; NaN for no value.  std (ddof 1): avg = the float64 sum over
+ *                               the count, the float64 sum of (avg - v)^2 over count - 1, the root in float32 for a
+ *                               float32 column and in float64 otherwise; NaN for fewer than two values.  `type` is a
+ *                               pmi_centers_type.  mean / std are written where the pointer is not NULL.  At most 64
+ *                               descriptors. */
+typedef struct pmi_kinetics_column {
+    const void *data;     /* device column */
+    double *mean;         /* device, n_groups entries, may be NULL */
+    double *std;          /* device, n_groups entries, may be NULL */
+    int32_t type;
+} pmi_kinetics_column;
+int pmi_kinetics_dark_order_dev(const int64_t *d_last, const int64_t *d_group, int64_t n, int64_t l_min, int64_t l_max,
+                                int64_t g_min, int64_t g_max, int32_t *d_rows, int64_t *d_last_sorted, int32_t *d_run,
+                                int32_t *d_start, void *stream);
+int pmi_kinetics_dark_search_dev(const int64_t *d_frame, const int32_t *d_rows, const int64_t *d_last_sorted,
+                                 const int32_t *d_run, const int32_t *d_start, int64_t n, int64_t max_frame,
+                                 int64_t *d_dark, void *stream);
+int pmi_kinetics_stats_dev(const int32_t *d_rows, const int32_t *d_start, int64_t n, int64_t n_groups,
+                           const pmi_kinetics_column *columns, int n_columns, void *stream);
 
 /* ---- timing hooks for bench.py (HIP events on the given stream) ------- */
 int pmi_event_create(void **event);

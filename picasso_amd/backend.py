@@ -1117,3 +1117,73 @@ class CenterGroups:
                 _dptr(d_x), tx, _dptr(d_y), ty, _dptr(self.group), self.g_min, self.g_max, _dptr(self.start), self.n,
                 self.n_groups, _dptr(area), ctypes.c_void_p(self.stream)), "pmi_centers_hull_dev")
             return area.cpu().numpy()
+
+
+# ---- dark times and group properties (csrc/kinetics.hip, picasso/postprocess.py:1985-2004, :3580-3649) ----
+KINETICS_MAX_COLUMNS = 64          # descriptors per pmi_kinetics_stats_dev call
+KINETICS_FRAME_LIMIT = 2 ** 62     # |frame|, |last_frame| below it: the signed 64-bit difference cannot overflow
+
+
+class _KineticsColumn(ctypes.Structure):
+    _fields_ = [("data", ctypes.c_void_p), ("mean", ctypes.c_void_p), ("std", ctypes.c_void_p), ("type", ctypes.c_int32)]
+
+
+class DarkTable:
+    """frame, last_frame and group of a table of binding events as int64 device columns, ordered once by
+    (group, last_frame) (pmi_kinetics_dark_order_dev); ``search()`` is one bisection per row."""
+
+    def __init__(self, frame, group, last_frame):
+        import torch
+        _lib.require_gpu()
+        frame, group, last_frame = (_index_column(a, what) for a, what in
+                                    ((frame, "frame"), (group, "group"), (last_frame, "last_frame")))
+        self.n = int(len(frame))
+        if self.n == 0 or not (len(group) == len(last_frame) == self.n):
+            raise ValueError("frame, group and last_frame must have one length, of at least one row")
+        self.max_frame = int(frame.max())
+        self.frame, self.group, self.last = _to_device(frame), _to_device(group), _to_device(last_frame)
+        self.device = self.frame.device
+        self.stream = torch.cuda.current_stream(self.device).cuda_stream
+        self.rows = torch.empty(self.n, dtype=torch.int32, device=self.device)
+        self.last_sorted = torch.empty(self.n, dtype=torch.int64, device=self.device)
+        self.run = torch.empty(self.n, dtype=torch.int32, device=self.device)
+        self.start = torch.empty(self.n + 1, dtype=torch.int32, device=self.device)
+        with _lib.lock():
+            _lib.check(_lib.load().pmi_kinetics_dark_order_dev(
+                _dptr(self.last), _dptr(self.group), self.n, int(last_frame.min()), int(last_frame.max()),
+                int(group.min()), int(group.max()), _dptr(self.rows), _dptr(self.last_sorted), _dptr(self.run),
+                _dptr(self.start), ctypes.c_void_p(self.stream)), "pmi_kinetics_dark_order_dev")
+
+    def search(self) -> np.ndarray:
+        """int64 dark time of every row, -1 where there is none."""
+        import torch
+        dark = torch.empty(self.n, dtype=torch.int64, device=self.device)
+        with _lib.lock():
+            _lib.check(_lib.load().pmi_kinetics_dark_search_dev(
+                _dptr(self.frame), _dptr(self.rows), _dptr(self.last_sorted), _dptr(self.run), _dptr(self.start), self.n,
+                self.max_frame, _dptr(dark), ctypes.c_void_p(self.stream)), "pmi_kinetics_dark_search_dev")
+            return dark.cpu().numpy()
+
+
+def group_mean_std(groups: "CenterGroups", columns):
+    """pandas' ``Series.mean()`` and ``Series.std()`` of every host column in ``columns`` per group of ``groups``
+    (pmi_kinetics_stats_dev) -> a list of (float64 mean, float64 std), one pair of arrays per column."""
+    import torch
+    G, out = groups.n_groups, []
+    columns = [_centers_column(c, "a statistics column") for c in columns]
+    for lo in range(0, len(columns), KINETICS_MAX_COLUMNS):
+        part = columns[lo:lo + KINETICS_MAX_COLUMNS]
+        desc = (_KineticsColumn * len(part))()
+        keep = []
+        for i, c in enumerate(part):
+            d = groups._dev(c)
+            mean = torch.empty(G, dtype=torch.float64, device=groups.device)
+            std = torch.empty(G, dtype=torch.float64, device=groups.device)
+            keep.append((d, mean, std))
+            desc[i] = _KineticsColumn(d.data_ptr(), mean.data_ptr(), std.data_ptr(), centers_type(c.dtype))
+        with _lib.lock():
+            _lib.check(_lib.load().pmi_kinetics_stats_dev(
+                _dptr(groups.rows), _dptr(groups.start), groups.n, G, ctypes.cast(desc, ctypes.c_void_p), len(part),
+                ctypes.c_void_p(groups.stream)), "pmi_kinetics_stats_dev")
+            out += [(mean.cpu().numpy(), std.cpu().numpy()) for _, mean, std in keep]
+    return out

@@ -838,7 +838,9 @@ def install(picasso_localize=None, picasso_gaussmle=None, picasso_gausslq=None, 
     undrift (``aim``, ``intersection_max``, ``intersection_max_z``), which the Localize GUI, Render and
     `picasso aim` call.  ``picasso.postprocess`` also gets ``link``, ``nena`` and the functions under them
     (``postprocess.LINK_NENA_NAMES``), and ``picasso.localize`` the two quick checks built on them, ``check_nena`` and
-    ``check_kinetics``, and the local density, distance histogram and pair correlation (``postprocess.PAIR_NAMES``).
+    ``check_kinetics``, and the local density, distance histogram and pair correlation (``postprocess.PAIR_NAMES``),
+    and the dark times and group properties (``postprocess.KINETICS_NAMES``: ``compute_dark_times``, ``dark_times``,
+    ``_dark_times``, ``groupprops``), which `picasso dark` and `picasso groupprops` call.
     ``picasso_clusterer`` (default: ``picasso.clusterer`` when it imports) gets DBSCAN, the SMLM
     clusterer, the frame analysis and the cluster centers, ``find_cluster_centers`` with the helpers under it
     (``clusterer.CLUSTERER_NAMES``); HDBSCAN, ``cluster_areas`` and ``test_subclustering`` stay its own."""
@@ -896,7 +898,7 @@ def install(picasso_localize=None, picasso_gaussmle=None, picasso_gausslq=None, 
     picasso_postprocess = _reference_module(picasso_postprocess, "postprocess")
     if picasso_postprocess is not None:
         from . import postprocess as amd_pp
-        for name in ("segment", "undrift") + amd_pp.LINK_NENA_NAMES + amd_pp.PAIR_NAMES:
+        for name in ("segment", "undrift") + amd_pp.LINK_NENA_NAMES + amd_pp.PAIR_NAMES + amd_pp.KINETICS_NAMES:
             setattr(picasso_postprocess, name, getattr(amd_pp, name))
     picasso_aim = _reference_module(picasso_aim, "aim")
     if picasso_aim is not None:

@@ -4,7 +4,9 @@ the GPU render (csrc/render.hip) and cross-correlation (csrc/xcorr.hip), and lin
 (:2007-2071 ``link``, :2422-2821 the link groups and their combination, :1058-1119 ``nena``, :1165-1239 the
 next-frame neighbour distance histogram) on top of csrc/link.hip, and the local density, the distance histogram and the
 pair correlation (:37-204 the index blocks, :1582-1631 ``compute_local_density``, :1002-1055 ``distance_histogram``,
-:1505-1540 ``pair_correlation``) on top of csrc/pairs.hip.
+:1505-1540 ``pair_correlation``) on top of csrc/pairs.hip, and the dark times and group properties of qPAINT
+(:1920-2004 ``compute_dark_times`` / ``dark_times`` / ``_dark_times``, :3580-3649 ``groupprops``) on top of
+csrc/kinetics.hip.
 """
 from __future__ import annotations
 
@@ -25,6 +27,8 @@ LINK_NENA_NAMES = ("link", "_get_link_groups", "get_link_groups", "_link_loc_gro
                    "_next_frame_neighbor_distance_histogram", "next_frame_neighbor_distance_histogram")
 # ... and for the analyses over the index blocks
 PAIR_NAMES = ("_index_blocks_shape", "compute_local_density", "distance_histogram", "pair_correlation")
+# ... and for the dark times and the group properties
+KINETICS_NAMES = ("_dark_times", "dark_times", "compute_dark_times", "groupprops")
 _SEGMENT_RENDER = {"blur_method": "gaussian", "min_blur_width": 1}      # what undrift renders its segments with
 
 
@@ -407,3 +411,124 @@ def pair_correlation(locs: pd.DataFrame, info, bin_size: float, r_max: float):
         bins_lower = bins_lower[:-1]
     area = np.pi * bin_size * (2 * bins_lower + bin_size)
     return bins_lower, dh / area
+
+
+# ---- dark times (postprocess.py:1920-2004) --------------------------------------------------------------------
+def _group_labels(group) -> np.ndarray:
+    """The ``group`` argument as int64 labels.  Narrower than the reference: a floating array is taken when every value
+    is finite and integral (the reference's own ``np.zeros(len(locs))`` is), anything else is refused."""
+    group = np.asarray(group)
+    if group.ndim != 1:
+        raise ValueError(f"group must be a 1-D array, not an array of shape {group.shape}")
+    if group.dtype.kind in "iub":
+        if group.dtype == np.uint64 and len(group) and int(group.max()) >= 2 ** 63:
+            raise ValueError("group labels must fit a signed 64-bit integer")
+        return group.astype(np.int64, copy=False)
+    if group.dtype.kind != "f":
+        raise TypeError(f"group must be an array of integer labels (or of integral floating values), not {group.dtype}")
+    if not (np.isfinite(group).all() and (group == np.trunc(group)).all() and (np.abs(group) <= 2.0 ** 53).all()):
+        raise ValueError("a floating group array must hold finite, integral labels of at most 2**53")
+    return group.astype(np.int64)
+
+
+def _frame_numbers(a, what: str) -> np.ndarray:
+    """An integer column whose values the device may subtract as signed 64-bit integers, as numba subtracts them: two
+    unsigned 32-bit columns meet in uint64 and wrap there, and a wrapped difference is never below max_frame, as a
+    negative one is never above 0; every other pair of integer columns meets in int64.  uint64 (which numba subtracts
+    from a signed column in float64) and magnitudes from 2**62 on are outside that domain."""
+    a = np.asarray(a)
+    if a.dtype.kind not in "iu":
+        raise TypeError(f"{what} must be an integer column, not {a.dtype}")
+    if a.dtype == np.uint64:
+        raise ValueError(f"{what} must not be a uint64 column: numba subtracts it from a signed column in float64")
+    a = a.astype(np.int64, copy=False)
+    if len(a) and max(int(a.max()), -int(a.min())) >= backend.KINETICS_FRAME_LIMIT:
+        raise ValueError(f"{what} must stay below 2**62 in magnitude")
+    return a
+
+
+def _dark_times(frame, group, last_frame) -> np.ndarray:
+    """The dark time before every binding event (postprocess.py:1985-2004): the smallest ``frame[i] - last_frame[j]``
+    that is positive and below ``frame.max()`` over the other events j of the group, -1 where there is none.  The
+    array has the dtype numba gives ``max_frame * np.ones(N, dtype=np.int32)``: int64 for a uint32 or int64 ``frame``,
+    int32 for an int32 one.  An empty table raises NumPy's ValueError for ``frame.max()``, as the reference does."""
+    frame, last_frame = np.asarray(frame), np.asarray(last_frame)
+    labels = _group_labels(group)
+    f, lf = _frame_numbers(frame, "frame"), _frame_numbers(last_frame, "last_frame")
+    if not (len(f) == len(lf) == len(labels)):
+        raise ValueError("frame, group and last_frame must have one length")
+    frame.max()                              # the reference's first line: an empty table raises here
+    dark = backend.DarkTable(f, labels, lf).search()
+    return dark.astype(np.result_type(frame.dtype, np.int32), copy=False)
+
+
+def dark_times(locs: pd.DataFrame, group=None) -> np.ndarray:
+    """Dark times of the binding events ``locs`` (postprocess.py:1952-1982); ``group`` defaults to the ``group``
+    column and, without one, to one group of all events."""
+    frame = locs["frame"].to_numpy()
+    lens = locs["len"].to_numpy()
+    with np.errstate(over="ignore"):
+        last_frame = frame + lens - 1        # in the columns' own dtypes, as in the reference
+    if group is None:
+        if "group" in locs.columns:
+            group = locs["group"].to_numpy()
+        else:
+            group = np.zeros(len(locs))
+    dark = _dark_times(frame, group, last_frame)
+    return dark
+
+
+def compute_dark_times(locs: pd.DataFrame, group=None) -> pd.DataFrame:
+    """Adds the int32 column ``dark`` to ``locs`` IN PLACE, as the reference does, and returns the events that have a
+    dark time (postprocess.py:1920-1949)."""
+    if "len" not in locs.columns:
+        raise AttributeError("Length not found. Please link localizations first.")
+    dark = dark_times(locs, group)
+    locs["dark"] = np.int32(dark)
+    locs = locs[locs.dark != -1]
+    return locs
+
+
+# ---- group properties (postprocess.py:3580-3649) --------------------------------------------------------------
+def groupprops(locs: pd.DataFrame, callback: Callable[[int], None] | Literal["console"] | None = None) -> pd.DataFrame:
+    """Mean and standard deviation of every column per group (postprocess.py:3580-3649): ``group``, ``n_events``,
+    then ``<c>_mean``, ``<c>_std`` for every column in table order, and ``qpaint_idx = 1 / dark_mean``; events
+    without a dark time (``dark == -1``) are left out first.  A table without a ``dark`` column raises KeyError, as
+    in the reference (whose ``try`` expects an AttributeError that pandas does not raise).  All groups are computed in
+    one pass on the device; a callable ``callback`` then sees 0 .. n - 1 and n, ``"console"`` shows a tqdm bar."""
+    try:
+        locs = locs[locs["dark"] != -1]
+    except AttributeError:
+        pass
+    names = list(locs.columns)
+    out = OrderedDict()
+    if len(locs) == 0:
+        n = 0
+        group_ids = np.unique(locs["group"])
+        stats = [(np.zeros(0), np.zeros(0))] * len(names)
+        n_events = np.zeros(0, np.int64)
+    else:
+        groups = backend.CenterGroups(_group_labels(locs["group"].to_numpy()))
+        group_ids, n_events, n = groups.unique, groups.n_locs, groups.n_groups
+        stats = backend.group_mean_std(groups, [locs[c].to_numpy() for c in names])
+    with np.errstate(all="ignore"):
+        # the reference stores every scalar into a float64 frame and casts at the end
+        out["group"] = np.asarray(group_ids).astype(np.float64).astype(np.int32)
+        out["n_events"] = np.asarray(n_events).astype(np.float64).astype(np.int32)
+        for c, (mean, std) in zip(names, stats):
+            for key, held in ((c + "_mean", mean), (c + "_std", std)):
+                held = np.array(held, np.float64)
+                held[np.isnan(held)] = np.nan        # DataFrame.loc stores any NaN as pandas' own
+                out[key] = held.astype(np.float32)
+    if callback == "console":
+        from tqdm import tqdm
+        for _ in tqdm(range(n), desc="Calculating group statistics", unit="Groups"):
+            pass
+    elif callable(callback):
+        for i in range(n):
+            callback(i)
+        callback(n)
+    groups_df = pd.DataFrame(out)
+    if "dark_mean" in groups_df.columns:
+        groups_df["qpaint_idx"] = 1 / groups_df["dark_mean"]
+    return groups_df
