@@ -60,6 +60,8 @@
  *                      _fill_index_blocks, :1543-1579 _local_density (:1582-1631
  *                      compute_local_density), :960-999 _distance_histogram
  *                      (:1002-1055 distance_histogram, :1505-1540 pair_correlation)
+ *   pmi_knn_*          picasso/postprocess.py:3704-3739 nn_analysis, picasso/spinna.py:696-747
+ *                      get_NN_dist (scipy.spatial.KDTree(X2).query(X1, k))
  */
 #ifndef PICASSO_HIP_H
 #define PICASSO_HIP_H
@@ -670,6 +672,30 @@ int pmi_kinetics_dark_search_dev(const int64_t *d_frame, const int32_t *d_rows, 
                                  int64_t *d_dark, void *stream);
 int pmi_kinetics_stats_dev(const int32_t *d_rows, const int32_t *d_start, int64_t n, int64_t n_groups,
                            const pmi_kinetics_column *columns, int n_columns, void *stream);
+
+/* ---- nearest-neighbour distances (picasso/postprocess.py:3704-3739 nn_analysis, picasso/spinna.py:696-747 get_NN_dist,
+ * csrc/knn.hip, csrc/knn_search.h) ------------------------------------------------------------------------------- *
+ * Point sets are float64 device arrays of shape (rows, dims), row-major, dims 2 or 3, finite, at most 2^31 - 2 rows.
+ * Scratch comes from the library's arena; every call runs on `stream` and synchronises it.
+ *
+ * pmi_knn_limit       the largest k of a query (32).
+ * pmi_knn_order_dev   orders the set X2 for queries: lo / hi (host, 2 entries each) are the smallest and largest x and y
+ *                     of the set (anything when m = 0); *grid receives the uniform grid over that box, planned for
+ *                     queries of k neighbours (it serves any k).  d_sorted (m * dims) receives the rows sorted by cell,
+ *                     d_start (int32, room for max(m, 1) + 1) the first sorted row of every cell, closed by m.
+ * pmi_knn_query_dev   d_out[i * k + j] (n x k) = the j-th smallest float64 distance sqrt(dx * dx + dy * dy (+ dz * dz))
+ *                     from row i of X1 to the rows of the ordered set, +inf where the set has fewer than k rows: what
+ *                     scipy.spatial.KDTree(X2).query(X1, k) returns as distances, in every bit.  One ordered set
+ *                     serves any number of query sets. */
+typedef struct pmi_knn_grid {
+    double lo[2], w[2];   /* corner and cell size */
+    int32_t n[2];         /* cells in x and y */
+} pmi_knn_grid;
+int pmi_knn_limit(void);
+int pmi_knn_order_dev(const double *d_x2, int dims, int64_t m, const double *lo, const double *hi, int64_t k,
+                      double *d_sorted, int32_t *d_start, pmi_knn_grid *grid, void *stream);
+int pmi_knn_query_dev(const double *d_x1, int dims, int64_t n, const double *d_sorted, const int32_t *d_start, int64_t m,
+                      const pmi_knn_grid *grid, int64_t k, double *d_out, void *stream);
 
 /* ---- timing hooks for bench.py (HIP events on the given stream) ------- */
 int pmi_event_create(void **event);

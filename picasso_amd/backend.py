@@ -973,6 +973,84 @@ class BlockTable:
             return hist[:int(n_bins)].cpu().numpy().view(np.uint64)
 
 
+# ---- nearest-neighbour distances (csrc/knn.hip, picasso/postprocess.py:3704-3739, picasso/spinna.py:696-747) ----
+class _KnnGrid(ctypes.Structure):
+    _fields_ = [("lo", ctypes.c_double * 2), ("w", ctypes.c_double * 2), ("n", ctypes.c_int32 * 2)]
+
+
+def knn_limit() -> int:
+    """The largest number of neighbours of one query (a dropped self column counts)."""
+    return int(_lib.load().pmi_knn_limit())
+
+
+def knn_points(X) -> np.ndarray:
+    """A point set as the device takes it: float64, C-contiguous, (rows, 2 | 3)."""
+    X = np.ascontiguousarray(X, np.float64)
+    if X.ndim != 2 or X.shape[1] not in (2, 3):
+        raise ValueError(f"points must have shape (n, 2) or (n, 3), not {X.shape}")
+    return X
+
+
+class KnnIndex:
+    """A finite point set X2 ordered on the device by the cells of a uniform grid over its x / y box
+    (pmi_knn_order_dev), planned for queries of `k` neighbours; it then answers any number of query sets, with any k
+    up to knn_limit().  `X2` is a host array, or a float64 device tensor of the same shape with its host box `box` =
+    (lo, hi), the smallest and largest x and y."""
+
+    def __init__(self, X2, k: int, box=None):
+        import torch
+        if box is None:
+            X2 = knn_points(X2)
+        else:                                          # raw pointers go to the library: nothing is converted here
+            if (not isinstance(X2, torch.Tensor) or not X2.is_cuda or X2.dtype != torch.float64 or X2.dim() != 2
+                    or int(X2.shape[1]) not in (2, 3) or not X2.is_contiguous()):
+                raise ValueError("with a box the points must be a contiguous float64 device tensor of shape (n, 2) or (n, 3)")
+            lo, hi = box
+            if np.shape(lo) != (2,) or np.shape(hi) != (2,):
+                raise ValueError("the box is (lo, hi): the smallest x and y, and the largest")
+        _lib.require_gpu()
+        if box is None:
+            self.points = torch.from_numpy(X2).cuda()
+            lo, hi = np.zeros(2), np.zeros(2)
+            for a in range(2 if len(X2) else 0):       # column by column: a reduction along axis 0 is ten times slower
+                lo[a], hi[a] = X2[:, a].min(), X2[:, a].max()
+        else:
+            self.points = X2
+        self.m, self.dims = int(self.points.shape[0]), int(self.points.shape[1])
+        lo, hi = np.ascontiguousarray(lo, np.float64), np.ascontiguousarray(hi, np.float64)
+        self.device = self.points.device
+        self.stream = torch.cuda.current_stream(self.device).cuda_stream
+        self.sorted = torch.empty((max(self.m, 1), self.dims), dtype=torch.float64, device=self.device)
+        self.start = torch.empty(max(self.m, 1) + 1, dtype=torch.int32, device=self.device)
+        self.grid = _KnnGrid()
+        with _lib.lock():
+            _lib.check(_lib.load().pmi_knn_order_dev(
+                _dptr(self.points), self.dims, self.m, _lib.ptr(lo), _lib.ptr(hi), int(k), _dptr(self.sorted),
+                _dptr(self.start), ctypes.byref(self.grid), ctypes.c_void_p(self.stream)), "pmi_knn_order_dev")
+
+    def query_device(self, d_x1, k: int):
+        """(n, k) float64 device tensor of the distances from the rows of the float64 device tensor `d_x1`."""
+        import torch
+        if (not isinstance(d_x1, torch.Tensor) or d_x1.device != self.device or d_x1.dtype != torch.float64
+                or d_x1.dim() != 2 or int(d_x1.shape[1]) != self.dims or not d_x1.is_contiguous()):
+            raise ValueError(f"queries must be a contiguous float64 tensor of shape (n, {self.dims}) on {self.device}")
+        n = int(d_x1.shape[0])
+        out = torch.empty((max(n, 1), int(k)), dtype=torch.float64, device=self.device)
+        with _lib.lock():
+            _lib.check(_lib.load().pmi_knn_query_dev(
+                _dptr(d_x1), self.dims, n, _dptr(self.sorted), _dptr(self.start), self.m, ctypes.byref(self.grid),
+                int(k), _dptr(out), ctypes.c_void_p(self.stream)), "pmi_knn_query_dev")
+        return out[:n]
+
+    def query(self, X1, k: int) -> np.ndarray:
+        """(n, k) float64 distances from the rows of the host array `X1`, ascending, inf where the set has fewer rows."""
+        import torch
+        X1 = knn_points(X1)
+        if X1.shape[1] != self.dims:
+            raise ValueError(f"queries must have {self.dims} columns, not {X1.shape[1]}")
+        return self.query_device(torch.from_numpy(X1).to(self.device), k).cpu().numpy()
+
+
 # ---- cluster centers (csrc/centers.hip, picasso/clusterer.py:694-897) ----
 CENTERS_MEAN, CENTERS_XSUM, CENTERS_FIRST, CENTERS_EVENTS = 0, 1, 2, 3
 _CENTERS_TYPES = {np.dtype("float32"): 0, np.dtype("float64"): 1, np.dtype("uint32"): 2, np.dtype("int32"): 3,

@@ -825,7 +825,7 @@ def _reference_module(given, name: str):
 
 def install(picasso_localize=None, picasso_gaussmle=None, picasso_gausslq=None, picasso_zfit=None,
             picasso_render=None, picasso_imageprocess=None, picasso_postprocess=None, *, fused: bool = False,
-            devices=None, picasso_aim=None, picasso_clusterer=None) -> None:
+            devices=None, picasso_aim=None, picasso_clusterer=None, picasso_spinna=None) -> None:
     """Rebind the reference package's hot-path functions to this backend, so that
     picasso.__main__ and the GUI run on the GPU unchanged.  Modules not given are taken
     from the installed ``picasso`` package; the rows next to the path (z fit, render, RCC undrift) are rebound
@@ -843,7 +843,9 @@ def install(picasso_localize=None, picasso_gaussmle=None, picasso_gausslq=None, 
     ``_dark_times``, ``groupprops``), which `picasso dark` and `picasso groupprops` call.
     ``picasso_clusterer`` (default: ``picasso.clusterer`` when it imports) gets DBSCAN, the SMLM
     clusterer, the frame analysis and the cluster centers, ``find_cluster_centers`` with the helpers under it
-    (``clusterer.CLUSTERER_NAMES``); HDBSCAN, ``cluster_areas`` and ``test_subclustering`` stay its own."""
+    (``clusterer.CLUSTERER_NAMES``); HDBSCAN, ``cluster_areas`` and ``test_subclustering`` stay its own.
+    ``picasso.postprocess`` also gets the nearest-neighbour distances (``postprocess.NN_NAMES``: ``nn_analysis``), and
+    ``picasso_spinna``, when given, ``get_NN_dist``: the rest of SPINNA stays its own and calls it."""
     if picasso_localize is None:
         import picasso.localize as picasso_localize       # the installed reference
     if picasso_gaussmle is None:
@@ -898,7 +900,7 @@ def install(picasso_localize=None, picasso_gaussmle=None, picasso_gausslq=None, 
     picasso_postprocess = _reference_module(picasso_postprocess, "postprocess")
     if picasso_postprocess is not None:
         from . import postprocess as amd_pp
-        for name in ("segment", "undrift") + amd_pp.LINK_NENA_NAMES + amd_pp.PAIR_NAMES + amd_pp.KINETICS_NAMES:
+        for name in ("segment", "undrift") + amd_pp.LINK_NENA_NAMES + amd_pp.PAIR_NAMES + amd_pp.KINETICS_NAMES + amd_pp.NN_NAMES:
             setattr(picasso_postprocess, name, getattr(amd_pp, name))
     picasso_aim = _reference_module(picasso_aim, "aim")
     if picasso_aim is not None:
@@ -910,3 +912,7 @@ def install(picasso_localize=None, picasso_gaussmle=None, picasso_gausslq=None, 
         from . import clusterer as amd_clusterer
         for name in amd_clusterer.CLUSTERER_NAMES:
             setattr(picasso_clusterer, name, getattr(amd_clusterer, name))
+    if picasso_spinna is not None:
+        from . import spinna as amd_spinna
+        for name in amd_spinna.SPINNA_NAMES:
+            setattr(picasso_spinna, name, getattr(amd_spinna, name))

@@ -6,7 +6,7 @@ next-frame neighbour distance histogram) on top of csrc/link.hip, and the local 
 pair correlation (:37-204 the index blocks, :1582-1631 ``compute_local_density``, :1002-1055 ``distance_histogram``,
 :1505-1540 ``pair_correlation``) on top of csrc/pairs.hip, and the dark times and group properties of qPAINT
 (:1920-2004 ``compute_dark_times`` / ``dark_times`` / ``_dark_times``, :3580-3649 ``groupprops``) on top of
-csrc/kinetics.hip.
+csrc/kinetics.hip, and the nearest-neighbour distances (:3704-3739 ``nn_analysis``) on top of csrc/knn.hip.
 """
 from __future__ import annotations
 
@@ -29,6 +29,8 @@ LINK_NENA_NAMES = ("link", "_get_link_groups", "get_link_groups", "_link_loc_gro
 PAIR_NAMES = ("_index_blocks_shape", "compute_local_density", "distance_histogram", "pair_correlation")
 # ... and for the dark times and the group properties
 KINETICS_NAMES = ("_dark_times", "dark_times", "compute_dark_times", "groupprops")
+# ... and for the nearest-neighbour distances
+NN_NAMES = ("nn_analysis",)
 _SEGMENT_RENDER = {"blur_method": "gaussian", "min_blur_width": 1}      # what undrift renders its segments with
 
 
@@ -532,3 +534,66 @@ def groupprops(locs: pd.DataFrame, callback: Callable[[int], None] | Literal["co
     if "dark_mean" in groups_df.columns:
         groups_df["qpaint_idx"] = 1 / groups_df["dark_mean"]
     return groups_df
+
+
+# ---- nearest-neighbour distances (postprocess.py:3704-3739, spinna.py:696-747) ------------------------------------
+def _kdtree_points(X2) -> np.ndarray:
+    """``KDTree(X2)`` as far as it decides anything: the float64 points, refused where scipy refuses them."""
+    X2 = np.asarray(X2)
+    if X2.ndim != 2:
+        raise ValueError(f"data must be of shape (n, m), where there are n points of dimension m, not {X2.shape}")
+    X2 = np.ascontiguousarray(X2, np.float64)
+    if not np.isfinite(X2).all():
+        raise ValueError("data must be finite, check for nan or inf values")
+    return X2
+
+
+def _knn_table(points: np.ndarray, X1, k: int, index=None) -> np.ndarray:
+    """The distances of ``KDTree(points).query(X1, k)`` for a 2-D ``X1`` as a table: float64, always (N, k), inf where
+    the tree has fewer than k points.  scipy's own refusals come first and before any device work, then this package's
+    limits: 2 or 3 columns, and k at most ``backend.knn_limit()``.  ``index`` is a ``backend.KnnIndex`` of ``points``
+    made earlier."""
+    X1 = np.ascontiguousarray(X1, np.float64)
+    if not np.isfinite(X1).all():
+        raise ValueError("'x' must be finite, check for nan or inf values")
+    k = int(k)
+    if k < 1:
+        raise ValueError("zero-size array to reduction operation maximum which has no identity")
+    if points.shape[1] not in (2, 3):
+        raise NotImplementedError(f"nearest neighbours on the device take 2 or 3 dimensions, not {points.shape[1]}")
+    if X1.ndim != 2 or X1.shape[1] != points.shape[1]:
+        raise ValueError(f"x must consist of vectors of length {points.shape[1]} but has shape {X1.shape}")
+    limit = backend.knn_limit()
+    if k > limit:
+        raise ValueError(f"{k} neighbours per point (a dropped self column counts) exceed the device limit of {limit}")
+    if len(X1) == 0 or len(points) == 0:
+        distances = np.full((len(X1), k), np.inf)
+    else:
+        if index is None:
+            index = backend.KnnIndex(points, k)
+        distances = index.query(X1, k)
+    return distances
+
+
+def _kdtree_query(points: np.ndarray, X1, k: int, index=None) -> np.ndarray:
+    """``_knn_table`` in the shape scipy gives it: (N,) when one neighbour is asked for."""
+    table = _knn_table(points, X1, k, index)
+    return table[:, 0] if table.shape[1] == 1 else table
+
+
+def nn_analysis(X1, X2, nn_count: int) -> np.ndarray:
+    """Distances from every row of ``X1`` to its ``nn_count`` nearest rows of ``X2`` (postprocess.py:3704-3739),
+    float64 and ascending, in every bit what the reference's KDTree query returns.  When the two sets hold the same
+    values one more neighbour is found and the first column (the point itself) is dropped.  The reference's final
+    reshape does nothing, so ``nn_count == 1`` on two different sets returns a 1-D (N,) array; rows past the number
+    of points of ``X2`` are inf.  Non-finite coordinates and ``nn_count <= 0`` raise what scipy raises."""
+    if X1.shape[1] != X2.shape[1]:
+        raise ValueError("X1 and X2 must have the same number of dimensions.")
+    points = _kdtree_points(X2)
+    if np.array_equal(X1, X2):
+        if int(nn_count) + 1 == 1:               # the query of one neighbour is 1-D and has no column to drop
+            raise IndexError("too many indices for array: array is 1-dimensional, but 2 were indexed")
+        nn = _kdtree_query(points, X1, nn_count + 1)[:, 1:]
+    else:
+        nn = _kdtree_query(points, X1, nn_count)
+    return nn
