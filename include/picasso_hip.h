@@ -697,6 +697,56 @@ int pmi_knn_order_dev(const double *d_x2, int dims, int64_t m, const double *lo,
 int pmi_knn_query_dev(const double *d_x1, int dims, int64_t n, const double *d_sorted, const int32_t *d_start, int64_t m,
                       const pmi_knn_grid *grid, int64_t k, double *d_out, void *stream);
 
+/* ---- cluster combine and its nearest-cluster distances (picasso/postprocess.py:2174-2288 cluster_combine, :2291-2419
+ * cluster_combine_dist, csrc/combine.hip, csrc/segment_stats.h) ------------------------------------------------------ *
+ * Label columns are int64 device arrays IN THE CALLER'S ROW ORDER (the host widens any integer column).  At most
+ * 2^31 - 2 rows.  Scratch comes from the library's arena; every call runs on `stream` and synchronises it.
+ *
+ * pmi_combine_order_dev    orders the rows by (group - g_min, cluster - c_min) with two stable radix sorts; g_min / g_max
+ *                          and c_min / c_max are the smallest and largest label of the two columns.  A segment is a run of
+ *                          one (group, cluster) pair: groups ascend, clusters ascend within a group, rows keep their table
+ *                          order within a segment.  d_rows[p] (int32, n) = the row at sorted position p, d_start[s] (int32,
+ *                          room for n + 1) the first sorted position of segment s, closed by n, d_seg_group[s] /
+ *                          d_seg_cluster[s] (int64, n) its labels, d_group_start[g] (int32, room for n + 1) the first
+ *                          SEGMENT of group g, closed by *n_segments.  d_rows / d_start are a table of the kind
+ *                          pmi_centers_order_dev returns: pmi_kinetics_stats_dev takes them too.
+ * pmi_combine_stats_dev    per column descriptor and segment, as float64, where the pointer is not NULL:
+ *                            mean / std        pandas' Series.mean() / Series.std() (ddof 1), exactly as
+ *                                              pmi_kinetics_stats_dev computes them (one shared header).
+ *                            average           np.average(data, weights=weight) of two columns of ONE floating type T
+ *                                              (`type`; the host promotes as np.average does): the products rounded to T,
+ *                                              NumPy's add.reduce of the products and of the weights in T (pairwise, 8192-
+ *                                              element chunks), one division in T.  Nothing is skipped: NaN gives NaN.
+ *                            weight_sum        that sum of the weights; where it is exactly 0 np.average raises, and so
+ *                                              does the host.
+ *                          `type` is a pmi_centers_type.  At most 32 descriptors.
+ * pmi_combine_mindist_dev  d_points (n x dims float64, row-major, dims 2 or 3, caller's row order) with the order of
+ *                          pmi_combine_order_dev in which EVERY SEGMENT IS ONE ROW (n_segments = n is the host's to
+ *                          check).  d_min_dist[p] (float64, n, SORTED position p) = the smallest
+ *                          sqrt(((dx * dx) + (dy * dy)) (+ (dz * dz))) from that row to the other rows of its group, as
+ *                          scipy's cdist and np.amin give it: the row itself is left out by position, not by distance; a
+ *                          NaN stays; +inf for a group of one row.  With dims = 3, d_min_dist_xy[p] is the same over x
+ *                          and y alone (it may be NULL with dims = 2).  One workgroup per tile of 256 rows of one group,
+ *                          the group's rows streamed through LDS: quadratic in the rows of a group. */
+typedef struct pmi_combine_column {
+    const void *data;     /* device column */
+    const void *weight;   /* device column of the same type (average / weight_sum), else NULL */
+    double *mean;         /* device, n_segments entries, may be NULL */
+    double *std;          /* device, n_segments entries, may be NULL */
+    double *average;      /* device, n_segments entries, may be NULL */
+    double *weight_sum;   /* device, n_segments entries, may be NULL */
+    int32_t type;
+} pmi_combine_column;
+int pmi_combine_order_dev(const int64_t *d_group, const int64_t *d_cluster, int64_t n, int64_t g_min, int64_t g_max,
+                          int64_t c_min, int64_t c_max, int32_t *d_rows, int32_t *d_start, int64_t *d_seg_group,
+                          int64_t *d_seg_cluster, int32_t *d_group_start, int64_t *n_segments, int64_t *n_groups,
+                          void *stream);
+int pmi_combine_stats_dev(const int32_t *d_rows, const int32_t *d_start, int64_t n, int64_t n_segments,
+                          const pmi_combine_column *columns, int n_columns, void *stream);
+int pmi_combine_mindist_dev(const double *d_points, int dims, const int32_t *d_rows, const int32_t *d_start,
+                            const int32_t *d_group_start, int64_t n, int64_t n_segments, int64_t n_groups,
+                            double *d_min_dist, double *d_min_dist_xy, void *stream);
+
 /* ---- timing hooks for bench.py (HIP events on the given stream) ------- */
 int pmi_event_create(void **event);
 int pmi_event_record(void *event, void *stream);

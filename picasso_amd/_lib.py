@@ -133,6 +133,9 @@ SYMBOLS = {
     "pmi_knn_limit": (_i32, []),
     "pmi_knn_order_dev": (_i32, [_p, _i32, _i64, _p, _p, _i64, _p, _p, _p, _p]),
     "pmi_knn_query_dev": (_i32, [_p, _i32, _i64, _p, _p, _i64, _p, _i64, _p, _p]),
+    "pmi_combine_order_dev": (_i32, [_p, _p, _i64, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "pmi_combine_stats_dev": (_i32, [_p, _p, _i64, _i64, _p, _i32, _p]),
+    "pmi_combine_mindist_dev": (_i32, [_p, _i32, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p]),
     "pmi_event_create": (_i32, [_p]),
     "pmi_event_record": (_i32, [_p, _p]),
     "pmi_event_elapsed_ms": (_i32, [_p, _p, _p]),

@@ -1265,3 +1265,133 @@ def group_mean_std(groups: "CenterGroups", columns):
                 ctypes.c_void_p(groups.stream)), "pmi_kinetics_stats_dev")
             out += [(mean.cpu().numpy(), std.cpu().numpy()) for _, mean, std in keep]
     return out
+
+
+# ---- cluster combine (csrc/combine.hip, picasso/postprocess.py:2174-2419) ----
+COMBINE_MAX_COLUMNS = 32           # descriptors per pmi_combine_stats_dev call
+
+
+class _CombineColumn(ctypes.Structure):
+    _fields_ = [("data", ctypes.c_void_p), ("weight", ctypes.c_void_p), ("mean", ctypes.c_void_p),
+                ("std", ctypes.c_void_p), ("average", ctypes.c_void_p), ("weight_sum", ctypes.c_void_p),
+                ("type", ctypes.c_int32)]
+
+
+class CombineGroups(CenterGroups):
+    """The rows of a table in the order of their (``group``, ``cluster``) pair, sent to the device once
+    (pmi_combine_order_dev).  It is a ``CenterGroups`` whose labels are the pairs: ``n_groups`` counts the segments,
+    ``unique`` holds each segment's group label and ``clusters`` its cluster label (groups ascending, clusters
+    ascending within a group), ``n_locs`` the sizes, ``order()`` is ``np.lexsort((cluster, group))``; rows keep their
+    table order within a segment, so ``group_mean_std`` and the statistics below take it as it is.
+    ``group_offsets[g]`` is the first segment of the g-th distinct group, closed by the number of segments."""
+
+    def __init__(self, group, cluster):
+        import torch
+        _lib.require_gpu()
+        group, cluster = _index_column(group, "group"), _index_column(cluster, "cluster")
+        if group.ndim != 1 or cluster.ndim != 1 or len(group) == 0 or len(cluster) != len(group):
+            raise ValueError("group and cluster must be columns of one length, of at least one row")
+        self.n = int(len(group))
+        self.g_min, self.g_max = int(group.min()), int(group.max())
+        self.c_min, self.c_max = int(cluster.min()), int(cluster.max())
+        self.group, self.cluster = _to_device(group), _to_device(cluster)
+        self.device = self.group.device
+        self.stream = torch.cuda.current_stream(self.device).cuda_stream
+        self.rows = torch.empty(self.n, dtype=torch.int32, device=self.device)
+        self.start = torch.empty(self.n + 1, dtype=torch.int32, device=self.device)
+        self.group_start = torch.empty(self.n + 1, dtype=torch.int32, device=self.device)
+        seg_group = torch.empty(self.n, dtype=torch.int64, device=self.device)
+        seg_cluster = torch.empty(self.n, dtype=torch.int64, device=self.device)
+        S, G = ctypes.c_int64(0), ctypes.c_int64(0)
+        with _lib.lock():
+            _lib.check(_lib.load().pmi_combine_order_dev(
+                _dptr(self.group), _dptr(self.cluster), self.n, self.g_min, self.g_max, self.c_min, self.c_max,
+                _dptr(self.rows), _dptr(self.start), _dptr(seg_group), _dptr(seg_cluster), _dptr(self.group_start),
+                ctypes.byref(S), ctypes.byref(G), ctypes.c_void_p(self.stream)), "pmi_combine_order_dev")
+            self.n_groups = int(S.value)
+            self.n_outer = int(G.value)
+            self.unique = seg_group[:self.n_groups].cpu().numpy()
+            self.clusters = seg_cluster[:self.n_groups].cpu().numpy()
+            self.offsets = self.start[:self.n_groups + 1].cpu().numpy()
+            self.group_offsets = self.group_start[:self.n_outer + 1].cpu().numpy()
+        self.n_locs = np.diff(self.offsets).astype(np.int64)
+        self._cache = {}
+
+    def hull_areas(self, x, y):
+        raise NotImplementedError("convex hulls are per label of one column: use CenterGroups")
+
+
+def _combine_floats(a, what: str, dtype=None) -> np.ndarray:
+    """A host column for the weighted average: 1-D, float32 or float64, contiguous."""
+    a = np.ascontiguousarray(a if dtype is None else np.asarray(a).astype(dtype, copy=False))
+    if a.ndim != 1 or a.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise TypeError(f"{what} must be a float32 or float64 column, not {a.dtype} of shape {a.shape}")
+    return a
+
+
+def combine_stats(groups: "CombineGroups", moments=(), averages=()):
+    """Per segment of ``groups`` (pmi_combine_stats_dev): for every host column in ``moments`` pandas'
+    ``Series.mean()`` and ``Series.std()``; for every (column, weights) pair in ``averages``, both float32 or both
+    float64 (promote as ``np.average`` does before the call), ``np.average(column, weights=weights)`` and the sum of
+    the weights.  -> (list of (float64 mean, float64 std), list of (float64 average, float64 weight sum))."""
+    import torch
+    if not isinstance(groups, CombineGroups):
+        raise TypeError("groups must be a CombineGroups")
+    S = groups.n_groups
+    jobs = []
+    for c in moments:
+        c = _centers_column(c, "a statistics column")
+        if len(c) != groups.n:
+            raise ValueError("every column must have one entry per row of the table")
+        jobs.append(("moments", np.ascontiguousarray(c), None))
+    for x, w in averages:
+        x, w = _combine_floats(x, "an averaged column"), _combine_floats(w, "the weights")
+        if x.dtype != w.dtype or len(x) != groups.n or len(w) != groups.n:
+            raise ValueError("an averaged column and its weights must have one floating type and one entry per row")
+        jobs.append(("average", x, w))
+    out = []
+    for lo in range(0, len(jobs), COMBINE_MAX_COLUMNS):
+        part = jobs[lo:lo + COMBINE_MAX_COLUMNS]
+        desc = (_CombineColumn * len(part))()
+        keep = []
+        for i, (kind, c, w) in enumerate(part):
+            d = groups._dev(c)
+            d_w = groups._dev(w) if w is not None else None
+            a = torch.empty(S, dtype=torch.float64, device=groups.device)
+            b = torch.empty(S, dtype=torch.float64, device=groups.device)
+            keep.append((d, d_w, a, b))
+            if kind == "moments":
+                desc[i] = _CombineColumn(d.data_ptr(), None, a.data_ptr(), b.data_ptr(), None, None, centers_type(c.dtype))
+            else:
+                desc[i] = _CombineColumn(d.data_ptr(), d_w.data_ptr(), None, None, a.data_ptr(), b.data_ptr(),
+                                         centers_type(c.dtype, True))
+        with _lib.lock():
+            _lib.check(_lib.load().pmi_combine_stats_dev(
+                _dptr(groups.rows), _dptr(groups.start), groups.n, S, ctypes.cast(desc, ctypes.c_void_p), len(part),
+                ctypes.c_void_p(groups.stream)), "pmi_combine_stats_dev")
+            out += [(a.cpu().numpy(), b.cpu().numpy()) for _, _, a, b in keep]
+    return out[:len(moments)], out[len(moments):]
+
+
+def combine_min_distances(groups: "CombineGroups", points):
+    """``points``: float64, C-contiguous, (rows, 2 | 3), in table order; every segment of ``groups`` must be one row.
+    -> (min_dist, min_dist_xy | None): float64, one entry per SORTED position (``groups.order()``), the distance to the
+    nearest other row of the group over all columns and, with 3 columns, over x and y (pmi_combine_mindist_dev)."""
+    import torch
+    if not isinstance(groups, CombineGroups):
+        raise TypeError("groups must be a CombineGroups")
+    if (not isinstance(points, np.ndarray) or points.dtype != np.float64 or points.ndim != 2
+            or points.shape[1] not in (2, 3) or not points.flags.c_contiguous or len(points) != groups.n):
+        raise ValueError("points must be a C-contiguous float64 array of shape (rows of the table, 2 or 3)")
+    if groups.n_groups != groups.n:
+        raise ValueError("every (group, cluster) pair must be one row")
+    dims = int(points.shape[1])
+    d_points = torch.from_numpy(points).to(groups.device)
+    best = torch.empty(groups.n, dtype=torch.float64, device=groups.device)
+    best_xy = torch.empty(groups.n, dtype=torch.float64, device=groups.device) if dims == 3 else None
+    with _lib.lock():
+        _lib.check(_lib.load().pmi_combine_mindist_dev(
+            _dptr(d_points), dims, _dptr(groups.rows), _dptr(groups.start), _dptr(groups.group_start), groups.n,
+            groups.n_groups, groups.n_outer, _dptr(best), _dptr(best_xy) if best_xy is not None else None,
+            ctypes.c_void_p(groups.stream)), "pmi_combine_mindist_dev")
+        return best.cpu().numpy(), (best_xy.cpu().numpy() if best_xy is not None else None)

@@ -16,10 +16,12 @@
 // add.reduce of a contiguous array: an accumulator that starts at 0 and takes the pairwise sum of each 8192-element
 // chunk in order; pairwise is a serial loop below 8 elements, eight strided accumulators up to 128, and a split at
 // n / 2 rounded down to a multiple of 8 above.  One lane walks one group's run of the gathered, group-ordered column
-// (the order is pmi_centers_order_dev's).  C++ float and double, no contraction.
+// (the order is pmi_centers_order_dev's).  C++ float and double, no contraction.  The sums and the two pandas statistics
+// are segment_stats.h's, which combine.hip shares.
 //
 // Every loop is bounded by the row count; no float atomics; an inconsistent table gives an empty run.
 #include "rows_common.h"
+#include "segment_stats.h"
 
 #pragma clang fp contract(off)
 
@@ -29,12 +31,6 @@ namespace kinetics {
 using namespace rows;
 
 constexpr int MAX_COLS = 64;
-constexpr int32_t CHUNK = 8192;      // NumPy's buffer size, in elements
-constexpr int DEPTH = 16;            // a chunk halves at most 7 times before it is a 128-element block
-
-template <typename T> __device__ __forceinline__ T quiet_nan();
-template <> __device__ __forceinline__ float quiet_nan<float>() { return __builtin_nanf(""); }
-template <> __device__ __forceinline__ double quiet_nan<double>() { return __builtin_nan(""); }
 
 __device__ __forceinline__ bool row_ok(int32_t i, int32_t n) { return (uint32_t)i < (uint32_t)n; }
 
@@ -150,77 +146,6 @@ __global__ void gather_kernel(const T *__restrict__ data, const int32_t *__restr
     vs[p] = row_ok(i, n) ? (A)data[i] : (A)0;
 }
 
-// NumPy's pairwise sum of at most 128 terms: term(p) for p in [lo, lo + m)
-template <typename S, typename F>
-__device__ __forceinline__ S block_sum(F term, int32_t lo, int32_t m)
-{
-    if (m < 8) {
-        S res = 0;
-        for (int32_t i = 0; i < m; ++i) res += term(lo + i);
-        return res;
-    }
-    S r[8];
-    for (int k = 0; k < 8; ++k) r[k] = term(lo + k);
-    int32_t i = 8;
-    for (; i < m - (m % 8); i += 8)
-        for (int k = 0; k < 8; ++k) r[k] += term(lo + i + k);
-    S res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < m; ++i) res += term(lo + i);
-    return res;
-}
-
-// ... of one chunk: the recursion on an explicit stack.  A frame waits for its left half, then for its right half.
-template <typename S, typename F>
-__device__ S pairwise_sum(F term, int32_t lo, int32_t m)
-{
-    int32_t f_lo[DEPTH], f_m[DEPTH];
-    S f_left[DEPTH];
-    int f_state[DEPTH];
-    int sp = 0;
-    f_lo[0] = lo, f_m[0] = m, f_state[0] = 0, f_left[0] = 0;
-    sp = 1;
-    S ret = 0;
-    // every frame is visited three times and there are fewer than m / 32 + 2 of them
-    for (int32_t it = 0; it < 3 * (m / 32 + 2) && sp > 0; ++it) {
-        const int t = sp - 1;
-        const int32_t cm = f_m[t], clo = f_lo[t];
-        int32_t half = cm / 2;
-        half -= half % 8;
-        if (f_state[t] == 0) {
-            if (cm <= 128) {
-                ret = block_sum<S>(term, clo, cm);
-                --sp;
-            } else if (sp == DEPTH) {            // cannot happen within a chunk; it would sum serially, inside the run
-                ret = 0;
-                for (int32_t i = 0; i < cm; ++i) ret += term(clo + i);
-                --sp;
-            } else {
-                f_state[t] = 1;
-                f_lo[sp] = clo, f_m[sp] = half, f_state[sp] = 0, f_left[sp] = 0;
-                ++sp;
-            }
-        } else if (f_state[t] == 1) {
-            f_left[t] = ret;
-            f_state[t] = 2;
-            f_lo[sp] = clo + half, f_m[sp] = cm - half, f_state[sp] = 0, f_left[sp] = 0;      // sp < DEPTH: checked in state 0
-            ++sp;
-        } else {
-            ret = f_left[t] + ret;
-            --sp;
-        }
-    }
-    return ret;
-}
-
-// NumPy's add.reduce over [a, b)
-template <typename S, typename F>
-__device__ S reduce_sum(F term, int32_t a, int32_t b)
-{
-    S acc = 0;
-    for (int32_t lo = a; lo < b; lo += CHUNK) acc += pairwise_sum<S>(term, lo, min(CHUNK, b - lo));
-    return acc;
-}
-
 template <typename A>
 __global__ void stats_kernel(const A *__restrict__ vs, const int32_t *__restrict__ start, int32_t n, int32_t n_groups,
                              double *__restrict__ mean, double *__restrict__ sd)
@@ -229,29 +154,8 @@ __global__ void stats_kernel(const A *__restrict__ vs, const int32_t *__restrict
     if (g >= n_groups) return;
     int32_t a = start[g], b = start[g + 1];
     if (a < 0 || b > n || a > b) a = b = 0;      // an inconsistent start table: an empty run
-    int64_t nobs = 0;
-    for (int32_t p = a; p < b; ++p) nobs += vs[p] == vs[p] ? 1 : 0;
-    const A count = (A)nobs;
-    if (mean) {
-        const A sum = reduce_sum<A>([&](int32_t p) { const A v = vs[p]; return v == v ? v : (A)0; }, a, b);
-        mean[g] = nobs > 0 ? (double)(sum / count) : quiet_nan<double>();
-    }
-    if (sd) {
-        double out = quiet_nan<double>();
-        if (count > (A)1) {
-            const double total = reduce_sum<double>([&](int32_t p) { const A v = vs[p]; return v == v ? (double)v : 0.0; }, a, b);
-            const double avg = total / (double)count;
-            const double sq = reduce_sum<double>([&](int32_t p) {
-                const A v = vs[p];
-                const double d = avg - (double)v;
-                return v == v ? d * d : 0.0;
-            }, a, b);
-            const double var = sq / (double)(count - (A)1);
-            if constexpr (sizeof(A) == 4) out = (double)__builtin_sqrtf((float)var);
-            else out = __builtin_sqrt(var);
-        }
-        sd[g] = out;
-    }
+    if (mean) mean[g] = segstats::series_mean<A>(vs, a, b);
+    if (sd) sd[g] = segstats::series_std<A>(vs, a, b);
 }
 
 template <typename T, typename A>

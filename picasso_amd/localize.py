@@ -845,7 +845,9 @@ def install(picasso_localize=None, picasso_gaussmle=None, picasso_gausslq=None, 
     clusterer, the frame analysis and the cluster centers, ``find_cluster_centers`` with the helpers under it
     (``clusterer.CLUSTERER_NAMES``); HDBSCAN, ``cluster_areas`` and ``test_subclustering`` stay its own.
     ``picasso.postprocess`` also gets the nearest-neighbour distances (``postprocess.NN_NAMES``: ``nn_analysis``), and
-    ``picasso_spinna``, when given, ``get_NN_dist``: the rest of SPINNA stays its own and calls it."""
+    ``picasso_spinna``, when given, ``get_NN_dist``: the rest of SPINNA stays its own and calls it; and the cluster
+    combine (``postprocess.COMBINE_NAMES``: ``cluster_combine``, ``cluster_combine_dist``), which
+    `picasso cluster_combine` and `picasso cluster_combine_dist` call."""
     if picasso_localize is None:
         import picasso.localize as picasso_localize       # the installed reference
     if picasso_gaussmle is None:
@@ -900,7 +902,7 @@ def install(picasso_localize=None, picasso_gaussmle=None, picasso_gausslq=None, 
     picasso_postprocess = _reference_module(picasso_postprocess, "postprocess")
     if picasso_postprocess is not None:
         from . import postprocess as amd_pp
-        for name in ("segment", "undrift") + amd_pp.LINK_NENA_NAMES + amd_pp.PAIR_NAMES + amd_pp.KINETICS_NAMES + amd_pp.NN_NAMES:
+        for name in ("segment", "undrift") + amd_pp.LINK_NENA_NAMES + amd_pp.PAIR_NAMES + amd_pp.KINETICS_NAMES + amd_pp.NN_NAMES + amd_pp.COMBINE_NAMES:
             setattr(picasso_postprocess, name, getattr(amd_pp, name))
     picasso_aim = _reference_module(picasso_aim, "aim")
     if picasso_aim is not None:

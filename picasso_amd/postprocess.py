@@ -6,7 +6,9 @@ next-frame neighbour distance histogram) on top of csrc/link.hip, and the local 
 pair correlation (:37-204 the index blocks, :1582-1631 ``compute_local_density``, :1002-1055 ``distance_histogram``,
 :1505-1540 ``pair_correlation``) on top of csrc/pairs.hip, and the dark times and group properties of qPAINT
 (:1920-2004 ``compute_dark_times`` / ``dark_times`` / ``_dark_times``, :3580-3649 ``groupprops``) on top of
-csrc/kinetics.hip, and the nearest-neighbour distances (:3704-3739 ``nn_analysis``) on top of csrc/knn.hip.
+csrc/kinetics.hip, and the nearest-neighbour distances (:3704-3739 ``nn_analysis``) on top of csrc/knn.hip, and the
+cluster combine and its nearest-cluster distances (:2174-2288 ``cluster_combine``, :2291-2419 ``cluster_combine_dist``)
+on top of csrc/combine.hip.
 """
 from __future__ import annotations
 
@@ -31,6 +33,8 @@ PAIR_NAMES = ("_index_blocks_shape", "compute_local_density", "distance_histogra
 KINETICS_NAMES = ("_dark_times", "dark_times", "compute_dark_times", "groupprops")
 # ... and for the nearest-neighbour distances
 NN_NAMES = ("nn_analysis",)
+# ... and for the cluster combine
+COMBINE_NAMES = ("cluster_combine", "cluster_combine_dist")
 _SEGMENT_RENDER = {"blur_method": "gaussian", "min_blur_width": 1}      # what undrift renders its segments with
 
 
@@ -597,3 +601,131 @@ def nn_analysis(X1, X2, nn_count: int) -> np.ndarray:
     else:
         nn = _kdtree_query(points, X1, nn_count)
     return nn
+
+
+# ---- cluster combine (postprocess.py:2174-2419) ------------------------------------------------------------------
+def _combine_labels(locs: pd.DataFrame):
+    """The ``group`` and ``cluster`` columns as int64 labels, by the rule of ``_group_labels``.  Narrower than the
+    reference, which compares any values: non-integral or non-finite labels are refused (ValueError) before device
+    work."""
+    labels = []
+    for name in ("group", "cluster"):
+        try:
+            labels.append(_group_labels(locs[name].to_numpy()))
+        except TypeError as e:
+            raise ValueError(str(e).replace("group", name)) from None
+        except ValueError as e:
+            raise ValueError(str(e).replace("group", name)) from None
+    return labels
+
+
+def _average_pair(col: np.ndarray, weights: np.ndarray):
+    """``col`` and ``weights`` in the type ``np.average`` multiplies and sums them in."""
+    if col.dtype.kind in "iub":
+        dtype = np.result_type(col.dtype, weights.dtype, "f8")
+    else:
+        dtype = np.result_type(col.dtype, weights.dtype)
+    if dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise TypeError(f"the weighted average on the device takes float32 or float64, not {dtype}")
+    return col.astype(dtype, copy=False), weights.astype(dtype, copy=False)
+
+
+def cluster_combine(locs: pd.DataFrame) -> pd.DataFrame:
+    """One row per (``group``, ``cluster``) pair (postprocess.py:2174-2288), groups ascending and clusters ascending
+    within a group: ``group`` (float64), ``cluster`` (the column's dtype), ``mean_frame``, ``x``, ``y`` (``z``),
+    ``std_frame``, ``lpx``, ``lpy`` (``lpz``) as float32 and ``n`` as int32, with a RangeIndex, in the reference's
+    values: ``mean_frame`` / ``std_frame`` are pandas' ``Series.mean()`` / ``Series.std()`` of ``frame``, ``x`` .. are
+    ``np.average(column, weights=photons)`` in ``np.result_type`` of the two, ``lpx`` .. are ``Series.std()`` of the
+    column over ``np.sqrt(n)``; a cluster of one row has NaN ``std_frame`` and ``lp*``.  A cluster whose weights sum
+    to exactly zero raises ``np.average``'s ZeroDivisionError; an empty table raises ``pd.concat``'s ValueError.
+    Narrower than the reference: ``group`` and ``cluster`` must hold integers (or finite, integral floats), anything
+    else raises ValueError before device work.  All pairs are computed in one pass on the device."""
+    axes = ("x", "y", "z") if "z" in locs.columns else ("x", "y")
+    group, cluster = locs["group"], locs["cluster"]
+    columns = {c: locs[c].to_numpy() for c in ("frame", "photons") + axes}
+    if len(locs) == 0:
+        return pd.concat([], ignore_index=True)           # what the reference's loop over no group ends in
+    g_labels, c_labels = _combine_labels(locs)
+    pairs = [_average_pair(columns[a], columns["photons"]) for a in axes]
+    groups = backend.CombineGroups(g_labels, c_labels)
+    moments, averages = backend.combine_stats(groups, [columns["frame"]] + [columns[a] for a in axes], pairs)
+    if any((scl == 0.0).any() for _, scl in averages):
+        raise ZeroDivisionError("Weights sum to zero, can't be normalized")
+    n = groups.n_locs
+    out = OrderedDict()
+    with np.errstate(all="ignore"):
+        out["group"] = groups.unique.astype(np.float64)
+        out["cluster"] = groups.clusters.astype(cluster.to_numpy().dtype)
+        out["mean_frame"] = moments[0][0].astype(np.float32)
+        for a, (avg, _) in zip(axes, averages):
+            out[a] = avg.astype(np.float32)
+        out["std_frame"] = moments[0][1].astype(np.float32)
+        for a, (_, std) in zip(axes, moments[1:]):
+            out["lp" + a] = (std / np.sqrt(n)).astype(np.float32)
+        out["n"] = n.astype(np.int32)
+    return pd.DataFrame(out)
+
+
+def _check_combined(g_labels: np.ndarray, c_labels: np.ndarray) -> None:
+    """What the reference's loop runs into, group after group, before any device work: a group of one distinct cluster
+    takes ``np.amin`` of no distance, a group with a repeated cluster label builds a frame from arrays of two
+    lengths."""
+    order = np.lexsort((c_labels, g_labels))
+    gs, cs = g_labels[order], c_labels[order]
+    first = np.flatnonzero(np.r_[True, gs[1:] != gs[:-1]])
+    rows = np.diff(np.r_[first, len(gs)])
+    distinct = np.add.reduceat(np.r_[True, (gs[1:] != gs[:-1]) | (cs[1:] != cs[:-1])].astype(np.int64), first)
+    bad = np.flatnonzero((distinct == 1) | (distinct < rows))
+    if len(bad):
+        if distinct[bad[0]] == 1:
+            raise ValueError("zero-size array to reduction operation minimum which has no identity")
+        raise ValueError("All arrays must be of the same length")
+
+
+def cluster_combine_dist(locs: pd.DataFrame, pixelsize: float | None = None) -> pd.DataFrame:
+    """The table of ``cluster_combine`` with the distance from every cluster to the nearest other cluster of its group
+    (postprocess.py:2291-2419): ``min_dist`` over x, y and ``z / pixelsize`` when the table has ``z`` (``pixelsize`` 130
+    when None) plus ``mind_dist_xy`` (the reference's spelling) over x and y; a table without ``z`` gets ``min_dist``
+    over x and y only.  In the reference's values:
+
+    * Distance arithmetic: ``scipy.spatial.distance.cdist`` on the columns promoted to float64,
+      ``sqrt(((dx*dx) + (dy*dy)) + (dz*dz))`` without contraction; the minimum of the squares followed by one root
+      equals ``np.amin`` of the distances, because the root is monotone and correctly rounded.  The row itself is left
+      out by position: two clusters at one place are 0 apart.  The result is cast to float32.
+    * z scaling: ``z / pixelsize`` is the reference's own NumPy expression, computed on the host, so a float32 ``z``
+      stays float32 under a Python number and becomes float64 under an ``np.float64``.
+    * Column alignment: groups ascend; within a group ``cluster`` is ``np.unique``-sorted and ``min_dist[i]`` belongs
+      to the i-th SORTED cluster, while the copied columns (cast as the reference casts them: float32, ``n`` int32,
+      ``group`` as it is) stay in table order.  For a table that came from ``cluster_combine`` the two coincide; for
+      one that did not, the rows are misaligned the way the reference's are.
+    * A group of a single cluster raises ValueError (the reference's ``np.amin`` of an empty array), a cluster label
+      repeated within a group raises ValueError (pandas' length mismatch), an empty table raises ``pd.concat``'s
+      ValueError, and labels that are not integral raise ValueError: all before device work."""
+    three = "z" in locs.columns
+    names = ("mean_frame", "x", "y") + (("z",) if three else ()) + ("std_frame", "lpx", "lpy") + (("lpz",) if three else ())
+    group, cluster = locs["group"].to_numpy(), locs["cluster"].to_numpy()
+    held = {c: locs[c].to_numpy() for c in names + ("n",)}
+    if len(locs) == 0:
+        return pd.concat([], ignore_index=True)
+    g_labels, c_labels = _combine_labels(locs)
+    _check_combined(g_labels, c_labels)
+    if three:
+        pixelsize = 130 if pixelsize is None else pixelsize
+        points = np.stack((held["x"], held["y"], held["z"] / pixelsize), axis=1)
+    else:
+        points = np.array(locs[["x", "y"]])
+    points = np.ascontiguousarray(points, np.float64)                 # what cdist converts to
+    groups = backend.CombineGroups(g_labels, c_labels)
+    min_dist, min_dist_xy = backend.combine_min_distances(groups, points)
+    by_group = np.argsort(g_labels, kind="stable")                    # the reference's boolean mask per ascending group
+    out = OrderedDict()
+    with np.errstate(all="ignore"):
+        out["group"] = group[by_group]
+        out["cluster"] = groups.clusters.astype(cluster.dtype)
+        for c in names:
+            out[c] = held[c][by_group].astype(np.float32)
+        out["n"] = held["n"][by_group].astype(np.int32)
+        out["min_dist"] = min_dist.astype(np.float32)
+        if three:
+            out["mind_dist_xy"] = min_dist_xy.astype(np.float32)
+    return pd.DataFrame(out)
