@@ -685,12 +685,18 @@ int orc_avgroi(const float *spots, int64_t N, int box, float *theta6)
  * xatol 1e-5, maxiter 500) — Brent's golden-section / parabolic fminbound,
  * restated here from its published algorithm; call site picasso/zfit.py:359-363.
  * ---------------------------------------------------------------------- */
+/* x ** 0.5 is pow(x, 0.5): by IEEE 754 the square root of x, except that pow(-inf, 0.5) is +inf where sqrt(-inf) is
+ * NaN (numba's LLVM lowers it to exactly this select around sqrt).  libm's pow is not correctly rounded everywhere
+ * (glibc's moved 21 of 1500 ordinary fits off scipy's path, tests/test_zfit_host.py), sqrt is, so the root is taken
+ * with sqrt. */
+static inline double pow_half(double v) { return v == -INFINITY ? INFINITY : sqrt(v); }
+
 static inline double zfit_target(double z, float sx, float sy, const double *cx, const double *cy)
 {
     double z2 = z * z, z3 = z * z2, z4 = z * z3, z5 = z * z4, z6 = z * z5;
     double wx = cx[0] * z6 + cx[1] * z5 + cx[2] * z4 + cx[3] * z3 + cx[4] * z2 + cx[5] * z + cx[6];
     double wy = cy[0] * z6 + cy[1] * z5 + cy[2] * z4 + cy[3] * z3 + cy[4] * z2 + cy[5] * z + cy[6];
-    double ax = pow((double)sx, 0.5) - pow(wx, 0.5), ay = pow((double)sy, 0.5) - pow(wy, 0.5);
+    double ax = pow_half((double)sx) - pow_half(wx), ay = pow_half((double)sy) - pow_half(wy);
     return ax * ax + ay * ay;
 }
 

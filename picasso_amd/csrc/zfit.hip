@@ -21,12 +21,15 @@ namespace pmi {
 
 struct Calib { double cx[7], cy[7]; };
 
+// x ** 0.5 is pow(x, 0.5): sqrt(x), NaN for a negative or NaN x, except that IEEE pow(-inf, 0.5) is +inf
+__device__ __forceinline__ double pow_half(double v) { return v == -INFINITY ? INFINITY : sqrt(v); }
+
 __device__ __forceinline__ double z_target(double z, double ssx, double ssy, const Calib &c)
 {
     const double z2 = z * z, z3 = z * z2, z4 = z * z3, z5 = z * z4, z6 = z * z5;
     const double wx = c.cx[0] * z6 + c.cx[1] * z5 + c.cx[2] * z4 + c.cx[3] * z3 + c.cx[4] * z2 + c.cx[5] * z + c.cx[6];
     const double wy = c.cy[0] * z6 + c.cy[1] * z5 + c.cy[2] * z4 + c.cy[3] * z3 + c.cy[4] * z2 + c.cy[5] * z + c.cy[6];
-    const double ax = ssx - sqrt(wx), ay = ssy - sqrt(wy);     // x ** 0.5 of a negative is NaN, like sqrt
+    const double ax = ssx - pow_half(wx), ay = ssy - pow_half(wy);
     return ax * ax + ay * ay;
 }
 
@@ -40,7 +43,7 @@ __global__ __launch_bounds__(256) void zfit_kernel(const float *__restrict__ sx,
     if (d_n) { int64_t dn = *d_n; n = dn < n ? dn : n; }
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const double ssx = sqrt((double)sx[i]), ssy = sqrt((double)sy[i]);
+    const double ssx = pow_half((double)sx[i]), ssy = pow_half((double)sy[i]);
     const double xatol = 1e-5;
     const int maxfun = 500;
     const double sqrt_eps = sqrt(2.2e-16), golden_mean = 0.5 * (3.0 - sqrt(5.0));
