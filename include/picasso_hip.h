@@ -54,6 +54,8 @@
  *   pmi_cluster_*      picasso/clusterer.py:114-201 _cluster (the SMLM clusterer),
  *                      :34-111 _frame_analysis / frame_analysis, :410-445 _dbscan
  *   pmi_centers_*      picasso/clusterer.py:694-897 find_cluster_centers and its helpers
+ *   pmi_areas_*        picasso/clusterer.py:1068-1169 _cluster_area, cluster_areas (picasso/masking.py:408-446
+ *                      threshold_otsu)
  *   pmi_kinetics_*     picasso/postprocess.py:1985-2004 _dark_times (:1920-1982 compute_dark_times,
  *                      dark_times), :3580-3649 groupprops
  *   pmi_pairs_*        picasso/postprocess.py:37-94 get_index_blocks, :169-204
@@ -746,6 +748,55 @@ int pmi_combine_stats_dev(const int32_t *d_rows, const int32_t *d_start, int64_t
 int pmi_combine_mindist_dev(const double *d_points, int dims, const int32_t *d_rows, const int32_t *d_start,
                             const int32_t *d_group_start, int64_t n, int64_t n_segments, int64_t n_groups,
                             double *d_min_dist, double *d_min_dist_xy, void *stream);
+
+/* ---- cluster areas and volumes (picasso/clusterer.py:1068-1169 _cluster_area / cluster_areas, picasso/masking.py:408-446
+ * threshold_otsu, csrc/areas.hip) ------------------------------------------------------------------------------------ *
+ * d_rows / d_start are the group order of pmi_centers_order_dev.  The coordinates are device columns in the caller's row
+ * order, each float32 or float64 (a pmi_centers_type); the points of a group are those columns in their common type T
+ * (`f32` says it is float32), z divided by z_div and rounded to T.  One workgroup per group.  Every call runs on
+ * `stream` and synchronises it.
+ *
+ * pmi_areas_lds_bins    PMI_AREAS_LDS_BINS: an image of at most that many bins is built, blurred and thresholded in LDS
+ *                       (two float64 copies of it, 64 KiB: two workgroups fit a CU); larger ones in global scratch.
+ * pmi_areas_max_bins    PMI_AREAS_MAX_BINS: the most bins one image may have; the host refuses a larger one (MemoryError)
+ *                       before any image is built, and likewise an axis of more than that many bins.
+ * pmi_areas_shape_dev   d_geom[g]: per dimension the smallest and largest coordinate give np.arange(min, max + bin, bin)
+ *                       as NumPy computes it from scalars: with PT = float32 when T and the bin are both float32, else
+ *                       float64, len = ceil(((max + bin) - min) / bin) in PT (-1: not a number, -2: beyond int64),
+ *                       start = min, next = min + bin in PT; edge 0 is start, edge 1 next, edge i is
+ *                       start + i * (next - start) in float64.  bin_xy serves x and y, bin_z z.
+ * pmi_areas_image_dev   for each of the n_list groups d_list[k]: the float64 counts of np.histogramdd over those edges
+ *                       (searchsorted from the right, a value on the last edge in the last bin, rows outside dropped), the
+ *                       blur of scipy.ndimage.gaussian_filter(sigma=2) with the 17 host weights d_weights (axes in order,
+ *                       reflect, tmp = line[l] * w[8]; for j = 8 .. 1: tmp += (line[l - j] + line[l + j]) * w[8 - j]),
+ *                       threshold_otsu on np.histogram(image, 256), and d_area[g] (float32) = count(image >= threshold)
+ *                       / 4, or / (16 / 5) with three dimensions, evaluated in float64.  No contraction anywhere.
+ *                       d_offset == NULL: every listed image has at most PMI_AREAS_LDS_BINS bins and lives in LDS.
+ *                       Otherwise image k lives in d_scratch[d_offset[k] .. + 2 * bins) (float64 entries, scratch_len in
+ *                       all).  Both paths run the same arithmetic in the same order.  Groups without bins are the
+ *                       host's (area 0).  With want_group >= 0 the blurred image of that group is also copied to
+ *                       d_want_image (row-major, room for its bins). */
+#define PMI_AREAS_LDS_BINS 4096
+#define PMI_AREAS_MAX_BINS (1 << 24)
+typedef struct pmi_areas_columns {
+    const void *data[3];  /* x, y, z device columns (z NULL with two dimensions) */
+    int32_t type[3];      /* PMI_CENTERS_F32 / PMI_CENTERS_F64 */
+    int32_t dims;         /* 2 or 3 */
+    int32_t f32;          /* the common type of the columns is float32 */
+    double z_div;         /* the pixel size z is divided by */
+} pmi_areas_columns;
+typedef struct pmi_areas_geom {
+    double start[3], next[3];
+    int64_t len[3];       /* edges per dimension; bins are max(len - 1, 0) */
+} pmi_areas_geom;
+int pmi_areas_lds_bins(void);
+int pmi_areas_max_bins(void);
+int pmi_areas_shape_dev(const pmi_areas_columns *cols, const int32_t *d_rows, const int32_t *d_start, int64_t n,
+                        int64_t n_groups, double bin_xy, double bin_z, int bin_f32, pmi_areas_geom *d_geom, void *stream);
+int pmi_areas_image_dev(const pmi_areas_columns *cols, const int32_t *d_rows, const int32_t *d_start, int64_t n,
+                        int64_t n_groups, const pmi_areas_geom *d_geom, const int32_t *d_list, const int64_t *d_offset,
+                        int64_t n_list, double *d_scratch, int64_t scratch_len, const double *d_weights, float *d_area,
+                        int64_t want_group, double *d_want_image, void *stream);
 
 /* ---- timing hooks for bench.py (HIP events on the given stream) ------- */
 int pmi_event_create(void **event);

@@ -136,6 +136,10 @@ SYMBOLS = {
     "pmi_combine_order_dev": (_i32, [_p, _p, _i64, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p]),
     "pmi_combine_stats_dev": (_i32, [_p, _p, _i64, _i64, _p, _i32, _p]),
     "pmi_combine_mindist_dev": (_i32, [_p, _i32, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p]),
+    "pmi_areas_lds_bins": (_i32, []),
+    "pmi_areas_max_bins": (_i32, []),
+    "pmi_areas_shape_dev": (_i32, [_p, _p, _p, _i64, _i64, _f64, _f64, _i32, _p, _p]),
+    "pmi_areas_image_dev": (_i32, [_p, _p, _p, _i64, _i64, _p, _p, _p, _i64, _p, _i64, _p, _p, _i64, _p, _p]),
     "pmi_event_create": (_i32, [_p]),
     "pmi_event_record": (_i32, [_p, _p]),
     "pmi_event_elapsed_ms": (_i32, [_p, _p, _p]),

@@ -1197,6 +1197,145 @@ class CenterGroups:
             return area.cpu().numpy()
 
 
+# ---- cluster areas and volumes (csrc/areas.hip, picasso/clusterer.py:1068-1169) ----
+AREAS_SCRATCH_BINS = 1 << 25       # bins of the images one launch of the scratch path holds, two float64 copies of each
+_AREAS_GEOM = np.dtype([("start", np.float64, 3), ("next", np.float64, 3), ("len", np.int64, 3)])
+AREAS_LDS_BINS = 4096              # PMI_AREAS_LDS_BINS: the most bins of an image that stays in LDS
+AREAS_MAX_BINS = 1 << 24           # PMI_AREAS_MAX_BINS: the most bins of any image, and of any one axis
+
+
+def areas_limits():
+    """(AREAS_LDS_BINS, AREAS_MAX_BINS) as the loaded library has them; a library built with other bounds is refused."""
+    L = _lib.load()
+    limits = int(L.pmi_areas_lds_bins()), int(L.pmi_areas_max_bins())
+    if limits != (AREAS_LDS_BINS, AREAS_MAX_BINS):
+        raise _lib.HipBackendError(f"libpicasso_hip was built with the area bounds {limits}, this package with "
+                                   f"{(AREAS_LDS_BINS, AREAS_MAX_BINS)}")
+    return limits
+
+
+class _AreasColumns(ctypes.Structure):
+    _fields_ = [("data", ctypes.c_void_p * 3), ("type", ctypes.c_int32 * 3), ("dims", ctypes.c_int32),
+                ("f32", ctypes.c_int32), ("z_div", ctypes.c_double)]
+
+
+def areas_weights() -> np.ndarray:
+    """The 17 float64 weights of ``scipy.ndimage.gaussian_filter(sigma=2)`` (truncate 4: radius 8), as scipy's
+    ``_gaussian_kernel1d`` computes them with NumPy."""
+    x = np.arange(-8, 9)
+    phi = np.exp(-0.5 / (2.0 * 2.0) * x ** 2)
+    return phi / phi.sum()
+
+
+def areas_bins(unique, lens) -> np.ndarray:
+    """Host check of the edge counts ``lens`` (groups x dimensions, int64; -1 / -2 where NumPy's ``arange`` refuses the
+    length) of the groups labelled ``unique`` -> int64 bins of every group's image.  Raises what ``np.arange`` raises
+    for the first group it refuses, and ``MemoryError`` for the first group with more than ``AREAS_MAX_BINS`` bins in its
+    image or along one axis (NumPy builds every edge array, so the reference fails on a huge axis even beside an empty
+    one).  No device work."""
+    limit = AREAS_MAX_BINS
+    lens = np.asarray(lens, np.int64).reshape(len(unique), -1)
+    bins = np.prod(np.clip(lens - 1, 0, None).astype(np.float64), axis=1)
+    for g in np.flatnonzero((lens < 0).any(axis=1) | (lens > limit + 1).any(axis=1) | (bins > limit)):
+        for n in lens[g]:
+            if n == -1:
+                raise ValueError("arange: cannot compute length")
+            if n == -2:
+                raise ValueError("Maximum allowed size exceeded")
+        shape = " x ".join(str(max(int(n) - 1, 0)) for n in lens[g])
+        raise MemoryError(f"group {unique[g]}: its image of {shape} bins exceeds the limit of {limit} bins "
+                          "(the localization precision is too small for the extent of the group)")
+    return bins.astype(np.int64)
+
+
+class AreaImages:
+    """The images of ``_cluster_area`` for every group of a ``CenterGroups``: ``columns`` are the host columns x, y
+    (and z), each float32 or float64, ``z_div`` what z is divided by in their common type, ``bin_xy`` / ``bin_z`` the
+    bin sizes as NumPy scalars (their type decides the arithmetic of ``np.arange``).  The constructor computes the
+    extents and edge counts on the device (pmi_areas_shape_dev) and checks them on the host (``areas_bins``);
+    ``areas()`` builds, blurs and thresholds the images (pmi_areas_image_dev)."""
+
+    def __init__(self, groups: "CenterGroups", columns, z_div, bin_xy, bin_z):
+        import torch
+        self.groups, self.dims = groups, len(columns)
+        self.lds_bins, self.max_bins = areas_limits()
+        if self.dims not in (2, 3):
+            raise ValueError("the points have 2 or 3 columns")
+        columns = [np.asarray(c) for c in columns]
+        self.dtype = np.result_type(*columns)
+        for c in columns:
+            centers_type(c.dtype, True)
+        self._keep = [groups._dev(c) for c in columns]
+        self.cols = _AreasColumns()
+        for d, (c, t) in enumerate(zip(columns, self._keep)):
+            self.cols.data[d], self.cols.type[d] = t.data_ptr(), centers_type(c.dtype)
+        self.cols.dims, self.cols.f32 = self.dims, int(self.dtype == np.float32)
+        if self.dims == 3:
+            # ``X[:, 2] /= pixelsize``: a Python number takes the array's type, a NumPy float64 scalar keeps its own
+            weak = np.result_type(np.empty(0, self.dtype), z_div) == self.dtype
+            self.cols.z_div = float(self.dtype.type(z_div)) if weak else float(z_div)
+        else:
+            self.cols.z_div = 1.0
+        G = groups.n_groups
+        self.geom = torch.zeros(G * _AREAS_GEOM.itemsize, dtype=torch.uint8, device=groups.device)
+        bin_f32 = int(np.asarray(bin_xy).dtype == np.float32)
+        with _lib.lock():
+            _lib.check(_lib.load().pmi_areas_shape_dev(
+                ctypes.byref(self.cols), _dptr(groups.rows), _dptr(groups.start), groups.n, G, float(bin_xy), float(bin_z),
+                bin_f32, _dptr(self.geom), ctypes.c_void_p(groups.stream)), "pmi_areas_shape_dev")
+            self.host_geom = self.geom.cpu().numpy().view(_AREAS_GEOM)
+        self.lens = self.host_geom["len"][:, :self.dims]
+        self.bins = areas_bins(groups.unique, self.lens)
+
+    def shape(self, g: int) -> tuple:
+        return tuple(int(max(n - 1, 0)) for n in self.lens[g])
+
+    def _launch(self, listed, offsets, scratch, area, weights, want, want_image):
+        import torch
+        groups = self.groups
+        d_list = torch.from_numpy(np.ascontiguousarray(listed, np.int32)).to(groups.device)
+        d_off = None if offsets is None else torch.from_numpy(np.ascontiguousarray(offsets, np.int64)).to(groups.device)
+        with _lib.lock():
+            _lib.check(_lib.load().pmi_areas_image_dev(
+                ctypes.byref(self.cols), _dptr(groups.rows), _dptr(groups.start), groups.n, groups.n_groups,
+                _dptr(self.geom), _dptr(d_list), _dptr(d_off), len(listed), _dptr(scratch),
+                0 if scratch is None else int(scratch.numel()), _dptr(weights), _dptr(area), int(want),
+                _dptr(want_image), ctypes.c_void_p(groups.stream)), "pmi_areas_image_dev")
+
+    def areas(self, image_of=None, force_scratch: bool = False):
+        """float32 area (count / 4) or volume (count / (16 / 5)) of every group; 0 for a group without bins.  With
+        ``image_of`` (an index into the groups) -> (areas, that group's blurred float64 image).  ``force_scratch``
+        sends every image through the global scratch, whatever its size."""
+        import torch
+        device = self.groups.device
+        lds_bins = 0 if force_scratch else self.lds_bins
+        area = torch.zeros(self.groups.n_groups, dtype=torch.float32, device=device)
+        weights = torch.from_numpy(areas_weights()).to(device)
+        want = -1 if image_of is None else int(image_of)
+        want_image = None
+        if want >= 0:
+            want_image = torch.zeros(max(int(self.bins[want]), 1), dtype=torch.float64, device=device)
+        small = np.flatnonzero((self.bins > 0) & (self.bins <= lds_bins))
+        large = np.flatnonzero(self.bins > lds_bins)
+        if len(small):
+            self._launch(small, None, None, area, weights, want, want_image)
+        # the images of one launch share one allocation, each at the prefix sum of the sizes before it
+        ends = np.cumsum(self.bins[large])
+        before = ends - self.bins[large]
+        scratch, lo = None, 0
+        while lo < len(large):
+            hi = max(int(np.searchsorted(ends, before[lo] + AREAS_SCRATCH_BINS, side="right")), lo + 1)
+            need = 2 * int(ends[hi - 1] - before[lo])
+            if scratch is None or scratch.numel() < need:
+                scratch = torch.empty(need, dtype=torch.float64, device=device)
+            self._launch(large[lo:hi], 2 * (before[lo:hi] - before[lo]), scratch, area, weights, want, want_image)
+            lo = hi
+        out = area.cpu().numpy()
+        if want < 0:
+            return out
+        return out, want_image.cpu().numpy()[:int(self.bins[want])].reshape(self.shape(want))
+
+
 # ---- dark times and group properties (csrc/kinetics.hip, picasso/postprocess.py:1985-2004, :3580-3649) ----
 KINETICS_MAX_COLUMNS = 64          # descriptors per pmi_kinetics_stats_dev call
 KINETICS_FRAME_LIMIT = 2 ** 62     # |frame|, |last_frame| below it: the signed 64-bit difference cannot overflow

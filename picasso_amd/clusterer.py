@@ -1,6 +1,7 @@
-"""DBSCAN, the SMLM clusterer and the cluster centers of picasso.clusterer (picasso/clusterer.py:34-544, :665-897)
-on top of csrc/cluster.hip and csrc/centers.hip: the same signatures, defaults, warnings, errors, dtypes, ``info``
-entries and column handling, the same int32 label for every row and the same table of centers.
+"""DBSCAN, the SMLM clusterer, the cluster centers and the cluster areas of picasso.clusterer
+(picasso/clusterer.py:34-544, :665-897, :1068-1237) on top of csrc/cluster.hip, csrc/centers.hip and csrc/areas.hip:
+the same signatures, defaults, warnings, errors, dtypes, ``info`` entries and column handling, the same int32 label
+for every row, the same table of centers and the same area or volume of every cluster.
 
 The table handling stays the reference's own NumPy / pandas calls on the same dtypes (``z /= pixelsize`` on the
 float32 column, the float32 ``X[:, 2] *= radius_xy / radius_z``, the widening to float64 that its KDTree and
@@ -8,16 +9,26 @@ sklearn do); the neighbour search, the local maxima, the union of core rows, the
 analysis run on the device.  ``find_cluster_centers`` computes every per-cluster quantity on the device in pandas'
 own arithmetic (the group order, the Kahan means and sums, the Welford standard deviations, the binding events,
 ``first()`` and the 2-D hull area); the derived columns are the reference's NumPy lines on those arrays, and the
-volume of a 3-D hull stays its per-cluster scipy call on the host.  ``hdbscan``, ``cluster_areas`` and
-``test_subclustering`` are not here: they stay the reference's and work on the tables these functions return.
+volume of a 3-D hull stays its per-cluster scipy call on the host.  ``cluster_areas`` builds, blurs and thresholds
+every cluster's image on the device, one workgroup per cluster, in NumPy's and SciPy's own arithmetic (the edges of
+``np.arange``, the counts of ``np.histogramdd``, ``gaussian_filter(sigma=2)``, the Otsu threshold on
+``np.histogram(image, 256)``): the result is a count over 4 or over 16 / 5 and equals the reference's.  Only the median
+localization precision, one scalar, is the reference's pandas / NumPy call on the host.  ``test_subclustering`` is a
+host composition over the device's nearest-neighbour table.  ``hdbscan`` is not here: it stays the reference's and works
+on the tables these functions take and return.
 
 Edges, as the reference has them: an empty table gives empty labels from ``_cluster`` (and a ``ValueError`` from
 the frame analysis, which takes the maximum of no frames), a ``ValueError`` from ``_dbscan`` (sklearn wants one
 sample) and a ``ZeroDivisionError`` from ``cluster`` / ``dbscan``; coordinates that are not finite raise
 ``ValueError`` (scipy's KDTree and sklearn both refuse them).  ``find_cluster_centers`` raises the reference's
-``IndexError`` on an empty table and scipy's ``ValueError`` on a NaN coordinate.
+``IndexError`` on an empty table and scipy's ``ValueError`` on a NaN coordinate.  ``cluster_areas`` returns an empty
+table for an empty one, raises NumPy's ``ValueError`` where ``np.arange`` refuses a cluster's extent (a coordinate
+that is not finite, a median precision of 0 or NaN) and ``MemoryError``, naming the group, where a cluster's image
+would exceed ``backend.AREAS_MAX_BINS`` bins (the reference runs out of memory in NumPy there).
 """
 from __future__ import annotations
+
+from typing import Callable
 
 import numpy as np
 import pandas as pd
@@ -27,7 +38,7 @@ from . import __version__, backend, lib
 # what localize.install() rebinds on picasso.clusterer
 CLUSTERER_NAMES = ("_frame_analysis", "frame_analysis", "_cluster", "cluster_2D", "cluster_3D", "cluster", "_dbscan",
                    "dbscan", "extract_valid_labels", "_count_binding_events", "_cluster_convex_hulls",
-                   "_weighted_z_means", "find_cluster_centers")
+                   "_weighted_z_means", "find_cluster_centers", "cluster_areas", "test_subclustering")
 _FA_BINS = 20
 
 
@@ -357,3 +368,75 @@ def find_cluster_centers(locs: pd.DataFrame, pixelsize: float | None = None) -> 
     if "group_input" in locs.columns:
         columns["group_input"] = res[len(mean_cols) + 1]["sum"].astype(np.int32)
     return pd.DataFrame(columns)
+
+
+# ---- cluster areas (clusterer.py:1068-1237) ----
+def cluster_areas(
+    locs: pd.DataFrame,
+    info: list[dict],
+    progress: Callable[[int], None] | None = None,
+) -> pd.DataFrame:
+    """Area (2-D, ``"Area (LP^2)"``) or volume (3-D, ``"Volume (LP^3)"``) of every cluster of a table with a
+    ``group`` column, in units of the median localization precision (clusterer.py:1112-1169): the number of bins of
+    the cluster's blurred image (bins of LP / 2, 1.25 LP in z) at or above its Otsu threshold.  One row per distinct
+    label, -1 included, int32 ``group`` and float32 values equal to the reference's.  All clusters are computed on the
+    device; a callable ``progress`` then sees 1 .. the number of clusters, ``None`` shows a tqdm bar."""
+    assert (
+        "group" in locs.columns
+    ), "Localizations must contain 'group' column."
+    pixelsize = lib.get_from_metadata(info, "Pixelsize", raise_error=True)
+    has_z = "z" in locs.columns
+    area_key = "Area (LP^2)" if not has_z else "Volume (LP^3)"
+    lp = np.median(locs[["lpx", "lpy"]].mean(axis=1))
+    group_arr = locs["group"].to_numpy()
+    if len(group_arr) == 0:
+        return pd.DataFrame({"group": np.unique(group_arr).astype(np.int32), area_key: np.zeros(0, dtype=np.float32)})
+    columns = [locs[c].to_numpy() for c in (("x", "y", "z") if has_z else ("x", "y"))]
+    bin_size = lp / 2  # pixel size for rendering
+    bin_size_z = bin_size * 2.5
+    groups = backend.CenterGroups(group_arr)
+    images = backend.AreaImages(groups, columns, pixelsize, bin_size, bin_size_z)
+    areas = {"group": groups.unique.astype(np.int32), area_key: images.areas()}
+    n = groups.n_groups
+    if progress is None:
+        from tqdm import tqdm
+        for _ in tqdm(range(n), desc="Calculating cluster areas"):
+            pass
+    else:
+        for idx in range(n):
+            progress(idx + 1)
+    return pd.DataFrame(areas)
+
+
+def test_subclustering(
+    mols: pd.DataFrame,
+    info: list[dict],
+    clustering_dist: float = 25,
+    sparse_dist: float = 80,
+) -> tuple[lib.IntArray1D, lib.IntArray1D]:
+    """``n_events`` of the molecules whose nearest neighbour is closer than ``clustering_dist`` (nm) and of those whose
+    nearest neighbour is at least ``sparse_dist`` (nm) away (clusterer.py:1172-1237).  The distances are the device's
+    nearest-neighbour table of the molecules to themselves (two neighbours: the first is the molecule itself)."""
+    from . import postprocess
+    assert (
+        "n_events" in mols.columns
+    ), "The input molecules must have n_events attribute."
+    assert sparse_dist > clustering_dist, (
+        "The sparse distance must be larger than the clustering " "distance."
+    )
+    pixelsize = lib.get_from_metadata(info, "Pixelsize", raise_error=True)
+    if "z" in mols.columns:
+        coords = mols[["x", "y", "z"]].to_numpy()
+        coords[:, 2] /= pixelsize
+    else:
+        coords = mols[["x", "y"]].to_numpy()
+    distances = postprocess._knn_table(postprocess._kdtree_points(coords), coords, 2)
+    nnd1 = distances[:, 1]
+    close_nnd_idx = np.where(nnd1 < clustering_dist / pixelsize)[0]
+    far_nnd_idx = np.where(nnd1 >= sparse_dist / pixelsize)[0]
+    clustered_nevents = mols.iloc[close_nnd_idx]["n_events"].to_numpy()
+    sparse_nevents = mols.iloc[far_nnd_idx]["n_events"].to_numpy()
+    return clustered_nevents, sparse_nevents
+
+
+test_subclustering.__test__ = False      # a function of the package, not a test of it

@@ -843,7 +843,7 @@ def install(picasso_localize=None, picasso_gaussmle=None, picasso_gausslq=None, 
     ``_dark_times``, ``groupprops``), which `picasso dark` and `picasso groupprops` call.
     ``picasso_clusterer`` (default: ``picasso.clusterer`` when it imports) gets DBSCAN, the SMLM
     clusterer, the frame analysis and the cluster centers, ``find_cluster_centers`` with the helpers under it
-    (``clusterer.CLUSTERER_NAMES``); HDBSCAN, ``cluster_areas`` and ``test_subclustering`` stay its own.
+    (``clusterer.CLUSTERER_NAMES``), ``cluster_areas`` and ``test_subclustering`` among them; HDBSCAN stays its own.
     ``picasso.postprocess`` also gets the nearest-neighbour distances (``postprocess.NN_NAMES``: ``nn_analysis``), and
     ``picasso_spinna``, when given, ``get_NN_dist``: the rest of SPINNA stays its own and calls it; and the cluster
     combine (``postprocess.COMBINE_NAMES``: ``cluster_combine``, ``cluster_combine_dist``), which
