@@ -262,6 +262,19 @@ int pmi_localize_set_ranges(int ranges);
  * candidates; if a call finds more, *d_out_n reports the number of CANDIDATES (an upper bound of the rows needed), nothing is
  * fitted and the table is untouched, exactly as for a table that is too small.  0: the exact stage stays in the scan. */
 int pmi_localize_set_defer(int on);
+/* Accept-rate prior of the deferring scan.  A wave of the scan may emit its candidates undecided only while its own exact
+ * rounds keep three in four of them; what the waves of a scan measured — how many candidates they decided, how many of those
+ * they kept — is summed and handed to the scan of the call's second frame range and to the next call on the same device and
+ * scratch bank, whose waves start from it (and check it on their first 8 candidates) instead of each proving the rate to
+ * itself.  It changes who decides a candidate, never the table: the fit decides exactly.  The prior lives with the scratch of
+ * the (device, bank), next to a key of dtype, Y, X, roi, box and min_ng: a call with another key starts without one, and so
+ * does the first call after pmi_release_scratch, pmi_localize_set_defer or pmi_localize_reset_defer_prior.
+ * pmi_localize_last_scan_decisions: of the calling thread's last pmi_localize_mle_dev on its device and bank, out4 =
+ * (candidates range A decided in the scan, candidates it emitted undecided, the same two of range B; zeros for a range the
+ * call did not have and for a call that did not defer).  Synchronises the stream, like pmi_mle_last_flag_reasons.
+ * (Candidates decided by the rescan of a chunk whose plateau flooded the candidate ring are in neither count.) */
+int pmi_localize_reset_defer_prior(void);
+int pmi_localize_last_scan_decisions(int64_t *out4, void *stream);
 int pmi_localize_mle_dev(const void *d_movie, int dtype, int64_t F, int64_t Y, int64_t X,
                          int box, double min_ng, const int64_t *roi4, int64_t f_lo, int64_t f_hi,
                          double baseline, double sensitivity, double gain,

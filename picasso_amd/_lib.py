@@ -68,6 +68,8 @@ SYMBOLS = {
     "pmi_locs_from_fits_dev": (_i32, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _p, _i32, _p, _p]),
     "pmi_localize_set_ranges": (_i32, [_i32]),
     "pmi_localize_set_defer": (_i32, [_i32]),
+    "pmi_localize_reset_defer_prior": (_i32, []),
+    "pmi_localize_last_scan_decisions": (_i32, [_p, _p]),
     "pmi_localize_mle_dev": (_i32, [_p, _i32, _i64, _i64, _i64, _i32, _f64, _p, _i64, _i64, _f64, _f64, _f64,
                                     _f64, _i32, _i32, _p, _i64, _p, _p]),
     "pmi_gausslq_set_mode": (_i32, [_i32]),

@@ -895,11 +895,6 @@ __global__ void locs_from_fits_lq_kernel(const int32_t *__restrict__ frame, cons
 
 }  // namespace lq
 
-int identify_impl(const void *d_movie, int dtype, int64_t F, int64_t Y, int64_t X, int box, double min_ng,
-                  const int64_t *roi4, int64_t f_lo, int64_t f_hi, int64_t label_offset,
-                  int32_t *d_frame, int32_t *d_y, int32_t *d_x, float *d_ng, int64_t cap, int64_t *d_out_n,
-                  bool defer_exact, hipStream_t s);
-
 }  // namespace pmi
 
 extern "C" {
@@ -1024,7 +1019,7 @@ int pmi_localize_lq_dev(const void *d_movie, int dtype, int64_t F, int64_t Y, in
     fr.capc = cap;
     fr.cap = cap;
     fr.rejects = false;
-    fr.scan = [&](void *ids, int64_t lo, int64_t hi, int64_t *d_cnt, hipStream_t st) {
+    fr.scan = [&](void *ids, int64_t lo, int64_t hi, int64_t *d_cnt, int, hipStream_t st) {
         const Ids d = carve(ids);
         return identify_impl(d_movie, dtype, F, Y, X, box, min_ng, roi4, lo, hi, 0, d.f, d.y, d.x, d.ng, cap, d_cnt, false, st);
     };

@@ -889,11 +889,6 @@ __global__ void locs_from_fits_kernel(const int32_t *__restrict__ frame, const i
     ((float *)cols.c[16])[i] = sqrtf(c[5]);
 }
 
-int identify_impl(const void *d_movie, int dtype, int64_t F, int64_t Y, int64_t X, int box, double min_ng,
-                  const int64_t *roi4, int64_t f_lo, int64_t f_hi, int64_t label_offset,
-                  int32_t *d_frame, int32_t *d_y, int32_t *d_x, float *d_ng, int64_t cap, int64_t *d_out_n,
-                  bool defer_exact, hipStream_t s);
-
 }  // namespace pmi
 
 extern "C" {
@@ -1101,6 +1096,13 @@ static bool g_localize_defer = true;
 int pmi_localize_set_defer(int on)
 {
     pmi::g_localize_defer = on != 0;
+    pmi::defer_prior_reset();
+    return PMI_OK;
+}
+
+int pmi_localize_reset_defer_prior(void)
+{
+    pmi::defer_prior_reset();
     return PMI_OK;
 }
 
@@ -1148,14 +1150,24 @@ int pmi_localize_mle_dev(const void *d_movie, int dtype, int64_t F, int64_t Y, i
     LocCols lc;
     for (int c = 0; c < PMI_LOC_COLUMNS; c++) lc.c[c] = (char *)d_table + (size_t)c * cap * 4;
     FusedRanges fr;
+    // the accept-rate prior the deferring scans start from (pmi_common.h DeferWords), keyed by what the rate depends on
+    if (defer) {
+        DeferKey key;
+        key.dtype = dtype; key.box = box; key.Y = Y; key.X = X; key.min_ng = min_ng;
+        key.roi[0] = cy0; key.roi[1] = cx0; key.roi[2] = cy1; key.roi[3] = cx1;
+        const int rc = defer_prior_begin(key, &fr.defer_words, (hipStream_t)stream);
+        if (rc != PMI_OK) return rc;
+    } else defer_prior_none();
+    unsigned *const dwords = fr.defer_words;
     fr.ids_bytes = (size_t)capc * (16 + 15 * 4 + 1) + acc_blocks * sizeof(unsigned) + 16;
     fr.capc = capc;
     fr.cap = cap;
     fr.rejects = defer;
     // identify (candidates when deferred) over frames [lo, hi]
-    fr.scan = [&](void *ids, int64_t lo, int64_t hi, int64_t *d_cnt, hipStream_t st) {
+    fr.scan = [&](void *ids, int64_t lo, int64_t hi, int64_t *d_cnt, int range, hipStream_t st) {
         const Ids d = carve(ids);
-        return identify_impl(d_movie, dtype, F, Y, X, box, min_ng, roi4, lo, hi, 0, d.f, d.y, d.x, d.ng, capc, d_cnt, defer, st);
+        return identify_impl(d_movie, dtype, F, Y, X, box, min_ng, roi4, lo, hi, 0, d.f, d.y, d.x, d.ng, capc, d_cnt, defer, st,
+                             dwords ? dwords + DW_PRIOR : nullptr, dwords ? dwords + DW_STATS + 4 * range : nullptr);
     };
     // the fit of the rows *d_rows (with the exact stage of identify in its start-value kernel when deferred)
     fr.fit = [&](void *ids, const int64_t *d_rows, int range, hipStream_t st) {

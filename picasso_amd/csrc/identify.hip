@@ -359,7 +359,8 @@ static int launch_scan(const void *d_movie, const IdParams &p, const float *d_ta
 int launch_scan_u16_fast(const void *d_movie, int dtype, int64_t Y, int64_t X, int y0, int x0, int cy, int cx, int64_t f_lo,
                          int64_t label_off, int nframes, int box, double min_ng, const float *d_tab, Record *recs,
                          long long cap, unsigned long long *n_total, int *frame_count, hipStream_t s, bool *handled,
-                         const int *gate = nullptr, bool defer = false, const float *fmovie = nullptr, int gate_want = 0);
+                         const int *gate = nullptr, bool defer = false, const float *fmovie = nullptr, int gate_want = 0,
+                         const unsigned *prior_in = nullptr, unsigned *stats_out = nullptr);
 
 // float32 / int32 / uint32 movies that hold 16-bit counts (a camera's counts saved wide): the frames are narrowed to
 // uint16 — exactly, or not at all: any pixel that is not an integer in 0..65535 raises the chunk's flag — and take the
@@ -405,11 +406,12 @@ __global__ __launch_bounds__(256) void narrow_to_u16_kernel(const T *__restrict_
 
 // d_movie points at frame 0 of a stack holding at least frames [f_lo, f_hi].
 // Labels written = frame index + label_offset.  defer_exact (a fused MLE call): the packed scan may leave its exact stage to
-// the fit's start-value kernel and emit candidates (NG_DEFERRED_BITS, pmi_common.h).
+// the fit's start-value kernel and emit candidates (NG_DEFERRED_BITS, pmi_common.h); prior_in / stats_out: the accept-rate prior
+// its waves may start from and the words they add their own counts to (identify_fast.hip FastParams, runtime.hip DeferPrior).
 int identify_impl(const void *d_movie, int dtype, int64_t F, int64_t Y, int64_t X, int box, double min_ng,
                   const int64_t *roi4, int64_t f_lo, int64_t f_hi, int64_t label_offset,
                   int32_t *d_frame, int32_t *d_y, int32_t *d_x, float *d_ng, int64_t cap, int64_t *d_out_n,
-                  bool defer_exact, hipStream_t s)
+                  bool defer_exact, hipStream_t s, const unsigned *prior_in, unsigned *stats_out)
 {
     if (box < 3 || box > PMI_MAX_BOX || (box & 1) == 0) { set_error("box must be odd, 3..%d (got %d)", PMI_MAX_BOX, box); return PMI_ERR_ARG; }
     if (F < 0 || Y <= 0 || X <= 0 || Y > 65535 || X > 65535) { set_error("bad movie shape (%lld,%lld,%lld)", (long long)F, (long long)Y, (long long)X); return PMI_ERR_ARG; }
@@ -458,7 +460,7 @@ int identify_impl(const void *d_movie, int dtype, int64_t F, int64_t Y, int64_t 
         // register-pipelined packed-u16 scan (identify_fast.hip: uint16, uint8, int16) when the layout allows
         // (a fused call may leave the exact stage to its fit's start-value kernel: defer_exact)
         rc = launch_scan_u16_fast(d_movie, dtype, Y, X, p.y0, p.x0, p.cy, p.cx, f_lo, label_offset, p.nframes, box, min_ng,
-                                      d_tab, recs, cap, d_total, count, s, &fast, nullptr, defer_exact);
+                                      d_tab, recs, cap, d_total, count, s, &fast, nullptr, defer_exact, nullptr, 0, prior_in, stats_out);
         p.gate = nullptr;
         const bool wide = dtype == PMI_U32 || dtype == PMI_I32 || dtype == PMI_F32;
         static const bool no_narrow = tuning_env("PMI_IDENTIFY_NO_NARROW") != nullptr;
@@ -592,7 +594,7 @@ int pmi_identify_dev(const void *d_movie, int dtype, int64_t F, int64_t Y, int64
                      int32_t *d_x, float *d_ng, int64_t cap, int64_t *d_out_n, void *stream)
 {
     return pmi::identify_impl(d_movie, dtype, F, Y, X, box, min_ng, roi4, f_lo, f_hi, 0, d_frame, d_y, d_x, d_ng,
-                              cap, d_out_n, false, (hipStream_t)stream);
+                              cap, d_out_n, false, (hipStream_t)stream, nullptr, nullptr);
 }
 
 static size_t dtype_size(int dtype)

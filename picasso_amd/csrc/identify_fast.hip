@@ -140,6 +140,10 @@ struct FastParams {
     int filt_slack;            // counts by which later pixels may undercut the minimum seen so far before a chunk is run again
     float filt_slackf;         // the same for the key scans, in the pixels' own unit (not clamped to 16 bits: a 32-bit integer movie's threshold may be 1e9)
     int defer;                 // 1: a wave whose exact rounds accept most of its candidates may emit the rest undecided (net gradient NG_DEFERRED_BITS, pmi_common.h)
+    // Accept-rate prior of a fused call (both nullptr: none).  The accept rate is a property of the movie and the threshold, not of
+    // the wave: a launch may start its waves from what earlier launches measured instead of every wave proving it to itself.
+    const unsigned *prior_in;  // (seen, kept) of earlier launches, settled before this launch starts and written by nobody while it runs
+    unsigned *stats_out;       // this launch's sums over its waves: [0] candidates its exact rounds decided, [1] of those kept, [2] candidates emitted undecided
     const float *fmovie;       // PT_KEY: the float32 frames the keys in `movie` were made from (same frame indexing)
     int gate_want;             // the launch runs only while *gate equals this
     const int *gate;           // optional device flag: the launch does nothing unless it is 0 (32-bit movies narrowed to uint16, identify.hip)
@@ -182,6 +186,13 @@ struct FastParams {
 #define FAST_ROUND_WIDE 64
 #endif
 constexpr int fast_round(int H) { return H <= 4 ? FAST_ROUND_SMALL : FAST_ROUND_WIDE; }
+// A seeded wave (FastParams::prior_in) trusts a prior only when it rests on this many decided candidates — eight cold rounds of 32,
+// what a handful of waves decide before they defer — and then checks it on its own first DEFER_SEED_PROBE candidates.  The probe
+// halves the history and adds itself, and the three-in-four rule wants 32 seen: the seeded history is DEFER_SEED_SEEN = 48, so
+// that 24 + 8 reach the rule with the wave's own candidates a quarter of what it judges by.  Kept of the probe's eight that
+// the wave needs to go on deferring: prior 75 % -> 6, 86 % (a DNA-PAINT movie) -> 4, 95 % -> 1.
+constexpr unsigned DEFER_PRIOR_FLOOR = 256;
+constexpr int DEFER_SEED_SEEN = 48, DEFER_SEED_PROBE = 8;
 #ifndef FAST_MIN_WAVES
 #define FAST_MIN_WAVES 4      // waves per SIMD the register allocator must leave room for
 #endif
@@ -573,6 +584,28 @@ __global__ __launch_bounds__(64, fast_waves_per_simd(H, P, EDGE, PT)) void ident
     int ex_seen = 0, ex_kept = 0;
     bool defer_now = false;
     int defer_rounds = 0;
+    // Seeded start (p.prior_in): earlier launches with the same movie shape and threshold decided at least DEFER_PRIOR_FLOOR
+    // candidates in exact rounds.  The wave takes their accept rate as a history of DEFER_SEED_SEEN and, if that passes the
+    // three-in-four rule, starts deferring — after it has checked the rate on its own rows: its first round is a probe (the path
+    // of the one-in-sixteen probes above: the history is halved, the round is added) of its first DEFER_SEED_PROBE candidates
+    // and of no more (seed_probe).  A wave on rows where the prior is wrong thereby lands in the ordinary warm-up.
+    // The prior is read-only for the whole launch and the wave's own sums go to other words (p.stats_out): no wave ever sees
+    // what a sibling did, the candidates a launch decides itself are the same in every run.
+    // Compiled into the instances a fused call can ask to defer only (boxes up to 7 on 16- and 8-bit pixels): the others keep
+    // the registers they had.
+    constexpr bool PRIOR = H <= 3 && !pt_is_key(PT);
+    int tot_seen = 0, tot_kept = 0, tot_deferred = 0;
+    int seed_probe = 0;                                // > 0: the seeded wave's probe is still to come
+    if (PRIOR && p.defer && p.prior_in && filter) {
+        const unsigned pr_seen = p.prior_in[0], pr_kept = p.prior_in[1];
+        if (pr_seen >= DEFER_PRIOR_FLOOR && pr_kept <= pr_seen) {
+            ex_seen = DEFER_SEED_SEEN;
+            ex_kept = (int)(((unsigned long long)DEFER_SEED_SEEN * pr_kept + pr_seen / 2) / pr_seen);
+            defer_now = ex_kept * 4 >= ex_seen * 3;
+            if (defer_now) { defer_rounds = 15; trigger = seed_probe = DEFER_SEED_PROBE; }
+            else { ex_seen = 0; ex_kept = 0; }         // a prior below the rule: exactly the cold wave
+        }
+    }
 
     // ---- results: buffered in registers, appended KBUF rounds at a time with ONE slot-allocating atomic per flush
     // per wave on the counter of this block's shard (a single hot counter costs ~11 ns per atomic)
@@ -678,6 +711,7 @@ __global__ __launch_bounds__(64, fast_waves_per_simd(H, P, EDGE, PT)) void ident
         // a wave that defers still decides one round in sixteen itself: its accept rate follows the rows it is in (a wave that
         // starts on dense spots and then crosses shot-noise rows would otherwise hand every reject to the fit)
         const bool probe = defer_now && (++defer_rounds & 15) == 0;
+        const bool own = !defer_now || probe;              // this round is decided here
         if (lane < n) {
             const int q = (head + lane) & (LIST - 1);
             const unsigned e = s_pos[q];
@@ -699,12 +733,14 @@ __global__ __launch_bounds__(64, fast_waves_per_simd(H, P, EDGE, PT)) void ident
                 kept = first_max && (double)ng > p.min_ng;
             }
         }
-        if (p.defer && (!defer_now || probe)) {
+        if (p.defer && own) {
             if (probe) { ex_seen >>= 1; ex_kept >>= 1; }       // the history fades: two probes that reject most outweigh it
+            const int nk = (int)__popcll(__ballot(kept));
             ex_seen += n;
-            ex_kept += (int)__popcll(__ballot(kept));
+            ex_kept += nk;
+            if constexpr (PRIOR) { tot_seen += n; tot_kept += nk; }
             defer_now = ex_seen >= 32 && ex_kept * 4 >= ex_seen * 3;
-        }
+        } else if (PRIOR && p.defer) tot_deferred += n;
         head += n;
         if (++rounds == KBUF) flush();
     };
@@ -1183,6 +1219,10 @@ __global__ __launch_bounds__(64, fast_waves_per_simd(H, P, EDGE, PT)) void ident
             // (evaluating in place, inside the row loop, was tried: the scan's 120 live registers and the round's 50
             // do not fit, and the spills land in the row loop — 5.1 ms instead of 1.5)
             if (!filter || tail - head >= trigger || ring_full) {
+                if constexpr (PRIOR) {
+                    // (tail == head: a flooded chunk gave its entries back; the probe waits for candidates)
+                    if (seed_probe && tail > head) { exact_round(min(tail - head, seed_probe)); seed_probe = 0; }
+                }
                 while (tail - head >= 64) exact_round(64);
                 if (filter) {
                     if (tail - head >= ROUND || (trigger < ROUND && tail > head)) exact_round(tail - head);
@@ -1195,9 +1235,19 @@ __global__ __launch_bounds__(64, fast_waves_per_simd(H, P, EDGE, PT)) void ident
             o += dn;
         }
     }
+    if constexpr (PRIOR) {
+        if (seed_probe && tail > head) exact_round(min(tail - head, seed_probe));
+    }
     while (tail - head >= 64) exact_round(64);
     if (tail > head) exact_round(tail - head);
     flush();
+    // integer sums: the order the waves arrive in does not matter (one atomic add per non-zero word: three at the most)
+    if constexpr (PRIOR) {
+        if (p.stats_out && lane < 3) {
+            const unsigned v = (unsigned)(lane == 0 ? tot_seen : (lane == 1 ? tot_kept : tot_deferred));
+            if (v) atomicAdd(&p.stats_out[lane], v);
+        }
+    }
 }
 
 // rows in flight of the key scans (4-byte pixels: a row in flight is eight registers until its keys are built): box 13 with
@@ -1272,7 +1322,8 @@ static bool unit_vectors_match()
 int launch_scan_u16_fast(const void *d_movie, int dtype, int64_t Y, int64_t X, int y0, int x0, int cy, int cx, int64_t f_lo,
                          int64_t label_off, int nframes, int box, double min_ng, const float *d_tab, Record *recs,
                          long long cap, unsigned long long *n_total, int *frame_count, hipStream_t s, bool *handled,
-                         const int *gate, bool defer, const float *fmovie, int gate_want)
+                         const int *gate, bool defer, const float *fmovie, int gate_want, const unsigned *prior_in,
+                         unsigned *stats_out)
 {
     *handled = false;
     static const bool force_generic = tuning_env("PMI_IDENTIFY_GENERIC") != nullptr;
@@ -1306,6 +1357,7 @@ int launch_scan_u16_fast(const void *d_movie, int dtype, int64_t Y, int64_t X, i
     p.f_lo = f_lo; p.label_off = label_off; p.nframes = nframes; p.box = box; p.min_ng = min_ng; p.gate = gate;
     p.defer = defer && !fmovie ? 1 : 0;
     p.fmovie = fmovie; p.gate_want = gate_want;
+    p.prior_in = p.defer ? prior_in : nullptr; p.stats_out = p.defer ? stats_out : nullptr;
     p.segs = pack > 1 ? 1 : (nch + 63) / 64;
     // Rows per unit: long units amortise the 2H + 2 pipeline rows a unit spends on its halo, short ones balance the
     // persistent waves (every wave runs ceil(units / waves) units).  Pick the length with the least total work.

@@ -58,6 +58,7 @@ enum ScratchSlot {
     SCR_GATES,            // per-chunk flags of that copy
     SCR_STATS,            // flag statistics of the last MLE fit (re-fit count, count per criterion)
     SCR_LQ_STATS,         // the same of the last least-squares fit (spots fitted again, count per reason)
+    SCR_DEFER_PRIOR,      // accept-rate prior of the deferring scans and their per-range counts (DeferWords)
     SCR_NUM
 };
 int scratch(int slot, size_t bytes, void **ptr);
@@ -93,17 +94,53 @@ struct LastFitStats {
 // The schedule of the fused calls (pmi_localize_mle_dev, pmi_localize_lq_dev): identify, fit, table, with the frames cut in
 // two ranges when that pays (runtime.hip).  The caller supplies its parts; `ids` is one range's SCR_IDS buffer of ids_bytes.
 struct FusedRanges {
+    unsigned *defer_words = nullptr;   // DeferWords of a call whose scan may defer (else nullptr): fit_rows_kernel folds a range's counts into the prior
     size_t ids_bytes;
     int64_t capc;          // rows of a range's identification / fit arrays: the candidates it may hold
     int64_t cap;           // rows of the table
     bool rejects;          // the fit may reject candidates: `accepted` counts those it kept (else accepted == candidates)
-    std::function<int(void *ids, int64_t f_lo, int64_t f_hi, int64_t *d_cnt, hipStream_t st)> scan;
+    std::function<int(void *ids, int64_t f_lo, int64_t f_hi, int64_t *d_cnt, int range, hipStream_t st)> scan;
     std::function<int(void *ids, const int64_t *d_rows, int range, hipStream_t st)> fit;
     std::function<const unsigned *(void *ids)> accepted;
     std::function<int(void *ids, const int64_t *d_rows, const int64_t *d_row0, hipStream_t st)> table;
 };
 int fused_ranges(const FusedRanges &c, int pipeline, int64_t F, int64_t Y, int64_t X, int64_t f_lo, int64_t f_hi,
                  int64_t *d_out_n, hipStream_t s);
+
+// Accept-rate prior of the deferring scan (identify_fast.hip): 16 words of device memory per (device, user bank), in the outer
+// bank's SCR_DEFER_PRIOR.  A scan of frame range r reads the prior pair and adds its own counts to the statistics words of r;
+// the one-thread kernel queued behind it (fit_rows_kernel) folds them into the prior, keeps them for
+// pmi_localize_last_scan_decisions and clears them.  Range B's scan starts behind that kernel of range A (ev_scan_a) and the
+// next call's scan A behind both ranges: every scan reads a settled prior that nobody writes while it runs.
+enum DeferWords {
+    DW_PRIOR = 0,         // (seen, kept): candidates earlier scans decided in exact rounds, and how many of them they kept
+    DW_STATS = 4,         // + 4 * range: (decided, kept, emitted undecided, -) of the scan in flight
+    DW_LAST = 12,         // + 2 * range: (decided, emitted undecided) of the last call's scans
+    DW_NUM = 16
+};
+// The pair is halved while it holds more than this: a scan that decides a few tens of thousands of candidates outweighs what
+// the calls before it saw within a few calls (a movie whose density drifts), and the sums stay far from 2^32.
+constexpr unsigned DEFER_PRIOR_BOUND = 1u << 18;
+// Everything the accept rate depends on besides the pixels: a call with another key starts without a prior.
+struct DeferKey {
+    int dtype = -1, box = 0;
+    int64_t Y = 0, X = 0, roi[4] = {0, 0, 0, 0};
+    double min_ng = 0.0;
+    bool operator==(const DeferKey &o) const {
+        return dtype == o.dtype && box == o.box && Y == o.Y && X == o.X && roi[0] == o.roi[0] && roi[1] == o.roi[1] &&
+               roi[2] == o.roi[2] && roi[3] == o.roi[3] && min_ng == o.min_ng;
+    }
+};
+// The words of the calling thread's device and bank for a deferring call with this key, cleared on `s` when the key, the
+// buffer or the reset epoch is not what the last call left (no prior).  Call with the OUTER bank selected.
+int defer_prior_begin(const DeferKey &key, unsigned **words, hipStream_t s);
+void defer_prior_none();             // the calling thread's fused call does not defer: pmi_localize_last_scan_decisions reports zeros
+void defer_prior_reset();            // every (device, bank) starts its next call without a prior
+
+int identify_impl(const void *d_movie, int dtype, int64_t F, int64_t Y, int64_t X, int box, double min_ng,
+                  const int64_t *roi4, int64_t f_lo, int64_t f_hi, int64_t label_offset,
+                  int32_t *d_frame, int32_t *d_y, int32_t *d_x, float *d_ng, int64_t cap, int64_t *d_out_n,
+                  bool defer_exact, hipStream_t s, const unsigned *prior_in = nullptr, unsigned *stats_out = nullptr);
 
 struct Record {   // one identification, 16 B
     int32_t frame;

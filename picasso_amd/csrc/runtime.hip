@@ -150,6 +150,62 @@ int side_lane(int pipeline, SideLane **lane)
     return PMI_OK;
 }
 
+// ---- the accept-rate prior of the deferring scans (pmi_common.h DeferWords) -------------------------------------------------
+// Host side: per (device, user bank) the key of the call that left the words, the generation of their buffer and the reset epoch.
+struct DeferPriorState { bool has_key = false, last = false; DeferKey key; unsigned generation = 0, epoch = 0; const unsigned *words = nullptr; };
+static DeferPriorState g_defer_prior[PMI_MAX_DEVICES][SCR_USER_BANKS];
+static std::mutex g_defer_mu;
+static unsigned g_defer_epoch = 0;       // bumped by defer_prior_reset
+int defer_prior_begin(const DeferKey &key, unsigned **words, hipStream_t s)
+{
+    int dev = 0;
+    int rc = checked_device(&dev);
+    if (rc != PMI_OK) return rc;
+    void *ptr = nullptr;
+    if ((rc = scratch(SCR_DEFER_PRIOR, DW_NUM * sizeof(unsigned), &ptr)) != PMI_OK) return rc;
+    const unsigned gen = scratch_generation_of(dev, scratch_user_bank(), SCR_DEFER_PRIOR);
+    bool cold;
+    {
+        std::lock_guard<std::mutex> lk(g_defer_mu);
+        DeferPriorState &st = g_defer_prior[dev][scratch_user_bank()];
+        cold = !st.has_key || !(st.key == key) || st.generation != gen || st.epoch != g_defer_epoch || st.words != ptr;
+        st.has_key = true; st.last = true; st.key = key; st.generation = gen; st.epoch = g_defer_epoch; st.words = (const unsigned *)ptr;
+    }
+    if (cold) PMI_HIP(hipMemsetAsync(ptr, 0, DW_NUM * sizeof(unsigned), s));
+    *words = (unsigned *)ptr;
+    return PMI_OK;
+}
+void defer_prior_none()
+{
+    std::lock_guard<std::mutex> lk(g_defer_mu);
+    g_defer_prior[current_device()][scratch_user_bank()].last = false;
+}
+void defer_prior_reset()
+{
+    std::lock_guard<std::mutex> lk(g_defer_mu);
+    g_defer_epoch++;
+}
+// (decided in the scan, emitted undecided) per range of the calling thread's last fused MLE call; zeros when it did not defer or
+// its words are gone
+static int defer_last_decisions(int64_t *out4, hipStream_t s)
+{
+    for (int i = 0; i < 4; i++) out4[i] = 0;
+    const unsigned *words = nullptr;
+    {
+        const int dev = current_device(), bank = scratch_user_bank();
+        const unsigned gen = scratch_generation_of(dev, bank, SCR_DEFER_PRIOR);
+        std::lock_guard<std::mutex> lk(g_defer_mu);
+        const DeferPriorState &st = g_defer_prior[dev][bank];
+        if (st.has_key && st.last && st.generation == gen) words = st.words;
+    }
+    if (!words) return PMI_OK;
+    PMI_HIP(hipStreamSynchronize(s));        // the call has joined its side stream to s before it returned
+    unsigned h[4];
+    PMI_HIP(hipMemcpy(h, words + DW_LAST, sizeof(h), hipMemcpyDeviceToHost));
+    for (int i = 0; i < 4; i++) out4[i] = h[i];
+    return PMI_OK;
+}
+
 int LastFitStats::record(int pipeline, int range, const unsigned *stats, hipStream_t s)
 {
     SideLane *lane = nullptr;
@@ -183,9 +239,22 @@ int LastFitStats::read(unsigned (&h)[16]) const
 // ---- the fused calls' frame ranges -----------------------------------------------------------------------------
 // rows: [0] rows of A to fit, [1] rows of B to fit, [2] rows of A for the table, [3] rows of B for the table, [4] row offset of B.
 // A range whose candidates overflow its arrays (their columns were not written) fits none of them.
-__global__ void fit_rows_kernel(const int64_t *__restrict__ n_cand, int64_t capc, int64_t *__restrict__ rows_fit)
+// A deferring scan (dw: its DeferWords, pmi_common.h) has added its counts to the statistics words of its range: they are folded
+// into the prior pair here, behind the scan and in front of whatever starts next — scan B waits for this kernel of range A,
+// the next call's scan A for both — kept for pmi_localize_last_scan_decisions, and cleared for the next scan of the range.
+__global__ void fit_rows_kernel(const int64_t *__restrict__ n_cand, int64_t capc, int64_t *__restrict__ rows_fit,
+                                unsigned *__restrict__ dw, int range)
 {
     *rows_fit = *n_cand > capc ? 0 : *n_cand;
+    if (dw) {
+        unsigned *st = dw + DW_STATS + 4 * range;
+        unsigned seen = dw[DW_PRIOR] + st[0], kept = dw[DW_PRIOR + 1] + st[1];
+        while (seen > DEFER_PRIOR_BOUND) { seen >>= 1; kept >>= 1; }       // old evidence fades
+        dw[DW_PRIOR] = seen; dw[DW_PRIOR + 1] = kept;
+        dw[DW_LAST + 2 * range] = st[0]; dw[DW_LAST + 2 * range + 1] = st[2];
+        if (range == 0) dw[DW_LAST + 2] = dw[DW_LAST + 3] = 0;             // (a call of one range)
+        st[0] = st[1] = st[2] = 0;
+    }
 }
 // The table rows once every count is known (cand_b == nullptr: one range; acc_* == nullptr: every candidate was kept).  A
 // range that overflowed its arrays: *d_out_n is the candidates' number, an upper bound of the rows; more rows than the
@@ -234,11 +303,11 @@ int fused_ranges(const FusedRanges &c, int pipeline, int64_t F, int64_t Y, int64
             table_rows(st);
             return rows + 2 + r;
         }
-        hipLaunchKernelGGL(fit_rows_kernel, dim3(1), dim3(1), 0, st, (const int64_t *)(n + r), c.capc, rows + r);
+        hipLaunchKernelGGL(fit_rows_kernel, dim3(1), dim3(1), 0, st, (const int64_t *)(n + r), c.capc, rows + r, c.defer_words, r);
         return rows + r;
     };
     if (!two) {
-        if ((rc = c.scan(ids[0], f_lo, f_hi, n, s)) != PMI_OK) return rc;
+        if ((rc = c.scan(ids[0], f_lo, f_hi, n, 0, s)) != PMI_OK) return rc;
         if ((rc = c.fit(ids[0], fit_rows(0, s), 0, s)) != PMI_OK) return rc;
     } else {
         SideLane *side_p = nullptr;
@@ -254,7 +323,7 @@ int fused_ranges(const FusedRanges &c, int pipeline, int64_t F, int64_t Y, int64
             ~Join() { if (!done) { (void)hipEventRecord(sd.ev_b, sd.s2); (void)hipStreamWaitEvent(st, sd.ev_b, 0); } }
         } join{side, s};
         // ---- range A on the caller's stream
-        if ((rc = c.scan(ids[0], lo, mid, n, s)) != PMI_OK) return rc;
+        if ((rc = c.scan(ids[0], lo, mid, n, 0, s)) != PMI_OK) return rc;
         const int64_t *rows_a = fit_rows(0, s);
         PMI_HIP(hipEventRecord(side.ev_scan_a, s));
         if ((rc = c.fit(ids[0], rows_a, 0, s)) != PMI_OK) return rc;
@@ -262,7 +331,7 @@ int fused_ranges(const FusedRanges &c, int pipeline, int64_t F, int64_t Y, int64
         PMI_HIP(hipStreamWaitEvent(side.s2, side.ev_scan_a, 0));
         const int outer = scratch_enter_inner();
         rc = scratch(SCR_IDS, c.ids_bytes, &ids[1]);
-        if (rc == PMI_OK) rc = c.scan(ids[1], mid + 1, hi, n + 1, side.s2);
+        if (rc == PMI_OK) rc = c.scan(ids[1], mid + 1, hi, n + 1, 1, side.s2);
         if (rc == PMI_OK) rc = c.fit(ids[1], fit_rows(1, side.s2), 1, side.s2);
         scratch_leave_inner(outer);
         if (rc != PMI_OK) return rc;
@@ -284,7 +353,7 @@ void release_fft_plans();   // xcorr.hip
 
 extern "C" {
 
-int pmi_version(void) { return 116; }   // 0.1.16: + pmi_areas_* (cluster areas and volumes); 0.1.15: + pmi_combine_* (cluster combine and its nearest-cluster distances); 0.1.14: + pmi_knn_* (nearest-neighbour distances); 0.1.13: + pmi_kinetics_* (dark times, group properties); 0.1.12: + pmi_centers_* (cluster centers); 0.1.11: + pmi_pairs_* (local density, distance histogram); 0.1.10: + pmi_cluster_* (DBSCAN, the SMLM clusterer); 0.1.9: + pmi_link_* / pmi_nena_hist_dev (link, NeNA); 0.1.8: - the pixel hand-off from the scan to the fit and its setter; 0.1.7: + pmi_aim_* (AIM undrift); 0.1.6: round 6 (32-bit integer movies on the key scan, side lanes per (device, bank); + pmi_mle_set_libm / pmi_mle_get_libm / pmi_libm_eval_dev)
+int pmi_version(void) { return 117; }   // 0.1.17: + pmi_localize_reset_defer_prior / pmi_localize_last_scan_decisions (accept-rate prior of the deferring scan); 0.1.16: + pmi_areas_* (cluster areas and volumes); 0.1.15: + pmi_combine_* (cluster combine and its nearest-cluster distances); 0.1.14: + pmi_knn_* (nearest-neighbour distances); 0.1.13: + pmi_kinetics_* (dark times, group properties); 0.1.12: + pmi_centers_* (cluster centers); 0.1.11: + pmi_pairs_* (local density, distance histogram); 0.1.10: + pmi_cluster_* (DBSCAN, the SMLM clusterer); 0.1.9: + pmi_link_* / pmi_nena_hist_dev (link, NeNA); 0.1.8: - the pixel hand-off from the scan to the fit and its setter; 0.1.7: + pmi_aim_* (AIM undrift); 0.1.6: round 6 (32-bit integer movies on the key scan, side lanes per (device, bank); + pmi_mle_set_libm / pmi_mle_get_libm / pmi_libm_eval_dev)
 
 const char *pmi_last_error(void) { return pmi::g_err; }
 
@@ -354,6 +423,11 @@ int pmi_memcpy_d2h_async(void *h, const void *d, size_t bytes, void *stream)
 }
 int pmi_release_scratch(void) { pmi::release_fft_plans(); return pmi::scratch_release_all(); }
 int pmi_scratch_bank(int bank) { return pmi::scratch_select_bank(bank); }
+int pmi_localize_last_scan_decisions(int64_t *out4, void *stream)
+{
+    if (!out4) { pmi::set_error("pmi_localize_last_scan_decisions: null pointer"); return PMI_ERR_ARG; }
+    return pmi::defer_last_decisions(out4, (hipStream_t)stream);
+}
 
 int pmi_event_create(void **event)
 {

@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """A/B on one box: pmi_localize_mle_dev with identify's exact stage in the scan (defer 0) and in the fit's start-value
 kernel (defer 1): the two tables must be equal bit for bit; time per pass for one and two ranges in flight.
-usage: python tools/ab_defer.py [frames] [box] [reps] [only] [eps]"""
+usage: python tools/ab_defer.py [--cold] [--two] [frames] [box] [reps] [only] [eps]
+--two: the profiled passes of `only` keep two frame ranges in flight, as bench.py's timed steps do (default: one).
+--cold: pmi_localize_reset_defer_prior before every call — the scan of range A starts without an accept-rate prior, so that what
+is left of the prior is its hand-over from range A to range B inside one call; the decisions of the last call are printed."""
 import ctypes, os, sys, time
+COLD = "--cold" in sys.argv
+TWO = "--two" in sys.argv
+sys.argv = [a for a in sys.argv if a not in ("--cold", "--two")]
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from picasso_amd import _lib, synth
@@ -21,13 +27,15 @@ dn = torch.zeros(1, dtype=torch.int64, device="cuda")
 
 
 def run(defer):
+    if COLD:
+        _lib.check(L.pmi_localize_reset_defer_prior(), "reset prior")
     rc = L.pmi_localize_mle_dev(ctypes.c_void_p(movie.data_ptr()), 0, F, 512, 512, box, 5000.0, None, 0, F - 1, 100.0, 1.0, 1.0, EPS, 100,
                                 _lib.MLE_METHODS["sigmaxy"], ctypes.c_void_p(tabs[defer].data_ptr()), cap, ctypes.c_void_p(dn.data_ptr()), None)
     _lib.check(rc, "localize")
 
 
 if only >= 0:
-    _lib.check(L.pmi_localize_set_ranges(1), "ranges")
+    _lib.check(L.pmi_localize_set_ranges(2 if TWO else 1), "ranges")
     _lib.check(L.pmi_localize_set_defer(only), "defer")
     for _ in range(10):
         run(only)
@@ -62,6 +70,9 @@ for rep in range(reps):
                 run(defer)
             torch.cuda.synchronize()
             dt = (time.perf_counter() - t0) / 20
-            print(f"ranges {ranges} defer {defer}: {dt * 1e3:.3f} ms per pass, {int(dn.item())} localizations", flush=True)
+            dec = (ctypes.c_int64 * 4)()
+            _lib.check(L.pmi_localize_last_scan_decisions(dec, None), "decisions")
+            print(f"ranges {ranges} defer {defer}{' cold' if COLD else ''}: {dt * 1e3:.3f} ms per pass, {int(dn.item())} localizations, "
+                  f"scan decided / left undecided per range {list(dec)}", flush=True)
 _lib.check(L.pmi_localize_set_defer(1), "defer")
 _lib.check(L.pmi_localize_set_ranges(2), "ranges")
