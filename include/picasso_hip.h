@@ -56,6 +56,8 @@
  *   pmi_centers_*      picasso/clusterer.py:694-897 find_cluster_centers and its helpers
  *   pmi_areas_*        picasso/clusterer.py:1068-1169 _cluster_area, cluster_areas (picasso/masking.py:408-446
  *                      threshold_otsu)
+ *   pmi_average_*      picasso/average.py:49-118 align_group_core, :354-530 average (the average image of
+ *                      picasso/render.py:739-773 render_hist_numba, the rotation and shift search, the transform)
  *   pmi_kinetics_*     picasso/postprocess.py:1985-2004 _dark_times (:1920-1982 compute_dark_times,
  *                      dark_times), :3580-3649 groupprops
  *   pmi_pairs_*        picasso/postprocess.py:37-94 get_index_blocks, :169-204
@@ -810,6 +812,50 @@ int pmi_areas_image_dev(const pmi_areas_columns *cols, const int32_t *d_rows, co
                         int64_t n_groups, const pmi_areas_geom *d_geom, const int32_t *d_list, const int64_t *d_offset,
                         int64_t n_list, double *d_scratch, int64_t scratch_len, const double *d_weights, float *d_area,
                         int64_t want_group, double *d_want_image, void *stream);
+
+/* ---- particle averaging (picasso/average.py:49-118 align_group_core, :354-530 average, csrc/average.hip) ------------- *
+ * d_rows / d_start are the group order of pmi_centers_order_dev; d_x / d_y are the float32 coordinates the reference
+ * keeps in its shared arrays, in the caller's row order.  The view is t_min < v < t_max (strict), the image n_pixel x
+ * n_pixel, all given as the host computed them in the reference's expressions.  Every call runs on `stream` and
+ * synchronises it.  csrc/average_core.h holds the arithmetic and compiles for the host.
+ *
+ * pmi_average_limits     PMI_AVERAGE_LDS_BINS: an average image of at most that many pixels is held in LDS by the align
+ *                        kernel (64 KiB of int32, with the 8 KiB pixel list two workgroups fit a CU), a larger one is
+ *                        read from global memory; PMI_AVERAGE_LIST: the rows of a group rotated at a time (larger groups
+ *                        go in tiles); PMI_AVERAGE_MAX_PIXELS: the most pixels per axis.
+ * pmi_average_image_dev  render_hist_numba of the table: d_image[row * n_pixel + column] (int32, zeroed here) counts the
+ *                        rows in view at int32(oversampling * (v - t_min)), the difference taken in float32 when sub_f32
+ *                        and the product in float32 when mul_f32 (NumPy's types for a float32 column), else in float64.
+ *                        *d_dropped counts rows in view whose pixel rounding carried outside the image (the reference
+ *                        fails on them).
+ * pmi_average_align_dev  per group and per chunk c of the angle list (angles c * ceil(n_angles / chunks) ...): over every
+ *                        angle a and every entry (iy, ix) of np.fft.fftshift of the circular cross-correlation of the
+ *                        group's image with d_image, the integer
+ *                            sum over the group's rows in view of d_image[(py - sy) mod n][(px - sx) mod n],
+ *                            (sy, sx) = ((iy - n / 2) mod n, (ix - n / 2) mod n),
+ *                        rows rotated as cos(a) * x - sin(a) * y, sin(a) * x + cos(a) * y in float64 with d_cos / d_sin,
+ *                        each operation rounded on its own.  d_parts[3 * (g * chunks + c)] = the largest value, then the
+ *                        lowest angle, then the lowest iy * n + ix; (0, -1, -1) when every value is 0.  use_lds: the
+ *                        image has at most PMI_AVERAGE_LDS_BINS pixels and is held in LDS; both paths give the same
+ *                        integers.  A sum must stay below 2^31: the caller checks rows-of-largest-group * max(image).
+ * pmi_average_apply_dev  d_choice[3 * g] = the chunks of group g reduced in the same order (value, angle index, flat index;
+ *                        (0, -1, -1): nothing chosen, the rows stay as they are), and for its rows
+ *                            x' = cos * x - sin * y - ceil(ix - n / 2) / oversampling, y' likewise with iy,
+ *                        in float64, stored as float32 in d_x_out / d_y_out (same row order as d_x / d_y). */
+#define PMI_AVERAGE_LDS_BINS 16384
+#define PMI_AVERAGE_LIST 2048
+#define PMI_AVERAGE_MAX_PIXELS 4096
+int pmi_average_limits(int *lds_bins, int *list, int *max_pixels);
+int pmi_average_image_dev(const float *d_x, const float *d_y, int64_t n, int64_t n_pixel, double t_min, double t_max,
+                          double oversampling, int sub_f32, int mul_f32, int32_t *d_image, int32_t *d_dropped, void *stream);
+int pmi_average_align_dev(const float *d_x, const float *d_y, const int32_t *d_rows, const int32_t *d_start, int64_t n,
+                          int64_t n_groups, int64_t n_pixel, double t_min, double t_max, double oversampling,
+                          const double *d_cos, const double *d_sin, int64_t n_angles, int64_t chunks,
+                          const int32_t *d_image, int use_lds, int32_t *d_parts, int32_t *d_dropped, void *stream);
+int pmi_average_apply_dev(const float *d_x, const float *d_y, const int32_t *d_rows, const int32_t *d_start, int64_t n,
+                          int64_t n_groups, int64_t n_pixel, double oversampling, const double *d_cos, const double *d_sin,
+                          int64_t n_angles, const int32_t *d_parts, int64_t chunks, int32_t *d_choice, float *d_x_out,
+                          float *d_y_out, void *stream);
 
 /* ---- timing hooks for bench.py (HIP events on the given stream) ------- */
 int pmi_event_create(void **event);

@@ -142,6 +142,11 @@ SYMBOLS = {
     "pmi_areas_max_bins": (_i32, []),
     "pmi_areas_shape_dev": (_i32, [_p, _p, _p, _i64, _i64, _f64, _f64, _i32, _p, _p]),
     "pmi_areas_image_dev": (_i32, [_p, _p, _p, _i64, _i64, _p, _p, _p, _i64, _p, _i64, _p, _p, _i64, _p, _p]),
+    "pmi_average_limits": (_i32, [_p, _p, _p]),
+    "pmi_average_image_dev": (_i32, [_p, _p, _i64, _i64, _f64, _f64, _f64, _i32, _i32, _p, _p, _p]),
+    "pmi_average_align_dev": (_i32, [_p, _p, _p, _p, _i64, _i64, _i64, _f64, _f64, _f64, _p, _p, _i64, _i64, _p, _i32, _p,
+                                     _p, _p]),
+    "pmi_average_apply_dev": (_i32, [_p, _p, _p, _p, _i64, _i64, _i64, _f64, _p, _p, _i64, _p, _i64, _p, _p, _p, _p]),
     "pmi_event_create": (_i32, [_p]),
     "pmi_event_record": (_i32, [_p, _p]),
     "pmi_event_elapsed_ms": (_i32, [_p, _p, _p]),

@@ -1534,3 +1534,124 @@ def combine_min_distances(groups: "CombineGroups", points):
             groups.n_groups, groups.n_outer, _dptr(best), _dptr(best_xy) if best_xy is not None else None,
             ctypes.c_void_p(groups.stream)), "pmi_combine_mindist_dev")
         return best.cpu().numpy(), (best_xy.cpu().numpy() if best_xy is not None else None)
+
+
+# ---- particle averaging (csrc/average.hip, picasso/average.py:49-118, :354-530) ----
+AVERAGE_LDS_BINS = 16384           # PMI_AVERAGE_LDS_BINS: the most pixels of an average image held in LDS
+AVERAGE_LIST = 2048                # PMI_AVERAGE_LIST: the rows of a group rotated at a time
+AVERAGE_MAX_PIXELS = 4096          # PMI_AVERAGE_MAX_PIXELS: the most pixels per axis
+AVERAGE_TARGET_BLOCKS = 4096       # workgroups the angle list is cut for when the groups are few
+AVERAGE_MIN_CHUNK = 8              # angles per chunk, at least
+
+
+def average_limits():
+    """(AVERAGE_LDS_BINS, AVERAGE_LIST, AVERAGE_MAX_PIXELS) as the loaded library has them; a library built with other
+    bounds is refused."""
+    vals = [ctypes.c_int(0) for _ in range(3)]
+    _lib.check(_lib.load().pmi_average_limits(*(ctypes.byref(v) for v in vals)), "pmi_average_limits")
+    limits = tuple(int(v.value) for v in vals)
+    if limits != (AVERAGE_LDS_BINS, AVERAGE_LIST, AVERAGE_MAX_PIXELS):
+        raise _lib.HipBackendError(f"libpicasso_hip was built with the averaging bounds {limits}, this package with "
+                                   f"{(AVERAGE_LDS_BINS, AVERAGE_LIST, AVERAGE_MAX_PIXELS)}")
+    return limits
+
+
+def average_geometry(oversampling, t_min, t_max):
+    """The reference's expressions for the image of ``render_hist_numba`` (picasso/render.py:765-770), evaluated by
+    NumPy in the types they come in: (n_pixel, sub_f32, mul_f32), the last two saying whether ``x - t_min`` and the
+    product with the oversampling are float32 operations for a float32 ``x``.  No device work."""
+    n_pixel = int(np.ceil(oversampling * (t_max - t_min)))
+    probe = np.zeros(1, np.float32) - t_min
+    scaled = oversampling * probe
+    for a in (probe, scaled):
+        if a.dtype not in (np.float32, np.float64):
+            raise TypeError(f"the view and the oversampling give {a.dtype} pixels; float32 or float64 expected")
+    return n_pixel, int(probe.dtype == np.float32), int(scaled.dtype == np.float32)
+
+
+def average_chunks(n_groups: int, n_angles: int) -> int:
+    """Chunks the angle list is cut into, so that a few groups still fill the device."""
+    want = -(-AVERAGE_TARGET_BLOCKS // max(int(n_groups), 1))
+    return int(max(1, min(want, n_angles // AVERAGE_MIN_CHUNK, 65536)))
+
+
+class AverageAligner:
+    """One alignment step of ``picasso.average`` for the groups of a table: the group order goes to the device once
+    (``CenterGroups``), the angle list once (``cos`` / ``sin`` taken per scalar angle on the host, as the reference
+    takes them); ``iteration()`` is one pass from a given state of the float32 coordinates."""
+
+    def __init__(self, group, angles):
+        self.groups = CenterGroups(group)
+        self.limits = average_limits()
+        angles = np.asarray(angles, np.float64)
+        self.n_angles = int(len(angles))
+        self.cos = np.array([np.cos(a) for a in angles], np.float64)
+        self.sin = np.array([np.sin(a) for a in angles], np.float64)
+        self.d_cos, self.d_sin = _to_device(self.cos), _to_device(self.sin)
+        self.max_group = int(self.groups.n_locs.max())
+
+    def iteration(self, x, y, oversampling, t_min, t_max, force_global: bool = False, chunks=None):
+        """``x``, ``y``: the float32 coordinates before the step.  -> dict with ``image`` (int32, n_pixel x n_pixel: the
+        average image), ``choice`` (int32, groups x 3: correlation value, angle index, flat index of the fftshifted
+        correlation; (0, -1, -1) where nothing was chosen), ``x`` / ``y`` (float32, aligned), ``chunks`` and ``ms``
+        (the three kernels' milliseconds by device events).  Raises ``ValueError`` before the align launch when a
+        correlation sum could reach 2**31, ``IndexError`` where the reference's histogram would index past its image."""
+        import torch
+        groups, L = self.groups, _lib.load()
+        x, y = np.ascontiguousarray(x), np.ascontiguousarray(y)
+        if x.dtype != np.float32 or y.dtype != np.float32 or len(x) != groups.n or len(y) != groups.n:
+            raise ValueError("x and y must be float32 columns with one entry per row of the table")
+        n_pixel, sub_f32, mul_f32 = average_geometry(oversampling, t_min, t_max)
+        if not 1 <= n_pixel <= self.limits[2]:
+            raise ValueError(f"an average image of {n_pixel} pixels per axis (1 .. {self.limits[2]} are supported)")
+        ov, lo, hi = float(oversampling), float(t_min), float(t_max)
+        use_lds = int(not force_global and n_pixel * n_pixel <= self.limits[0])
+        chunks = average_chunks(groups.n_groups, self.n_angles) if chunks is None else int(chunks)
+        dev, G, n = groups.device, groups.n_groups, groups.n
+        d_x, d_y = _to_device(x), _to_device(y)
+        image = torch.empty(n_pixel * n_pixel, dtype=torch.int32, device=dev)
+        dropped = torch.zeros(1, dtype=torch.int32, device=dev)
+        parts = torch.empty(3 * G * chunks, dtype=torch.int32, device=dev)
+        choice = torch.empty(3 * G, dtype=torch.int32, device=dev)
+        x_out, y_out = torch.empty_like(d_x), torch.empty_like(d_y)
+        stream = ctypes.c_void_p(groups.stream)
+        ms = {}
+
+        def timed(name, call):
+            t0, t1 = ctypes.c_void_p(), ctypes.c_void_p()
+            _lib.check(L.pmi_event_create(ctypes.byref(t0)), "pmi_event_create")
+            _lib.check(L.pmi_event_create(ctypes.byref(t1)), "pmi_event_create")
+            try:
+                _lib.check(L.pmi_event_record(t0, stream), "pmi_event_record")
+                call()
+                _lib.check(L.pmi_event_record(t1, stream), "pmi_event_record")
+                took = ctypes.c_float(0)
+                _lib.check(L.pmi_event_elapsed_ms(t0, t1, ctypes.byref(took)), "pmi_event_elapsed_ms")
+                ms[name] = float(took.value)
+            finally:
+                L.pmi_event_destroy(t0)
+                L.pmi_event_destroy(t1)
+
+        with _lib.lock():
+            timed("image", lambda: _lib.check(L.pmi_average_image_dev(
+                _dptr(d_x), _dptr(d_y), n, n_pixel, lo, hi, ov, sub_f32, mul_f32, _dptr(image), _dptr(dropped), stream),
+                "pmi_average_image_dev"))
+            host_image = image.cpu().numpy().reshape(n_pixel, n_pixel)
+            if int(dropped.cpu()[0]):
+                raise IndexError(f"index {n_pixel} is out of bounds for axis 0 with size {n_pixel}")
+            top = int(host_image.max())
+            if self.max_group * top >= 2 ** 31:
+                raise ValueError(f"a group of {self.max_group} rows against an average image that peaks at {top}: the "
+                                 "correlation could exceed 32 bits")
+            timed("align", lambda: _lib.check(L.pmi_average_align_dev(
+                _dptr(d_x), _dptr(d_y), _dptr(groups.rows), _dptr(groups.start), n, G, n_pixel, lo, hi, ov,
+                _dptr(self.d_cos), _dptr(self.d_sin), self.n_angles, chunks, _dptr(image), use_lds, _dptr(parts),
+                _dptr(dropped), stream), "pmi_average_align_dev"))
+            if int(dropped.cpu()[0]):
+                raise IndexError(f"index {n_pixel} is out of bounds for axis 0 with size {n_pixel}")
+            timed("apply", lambda: _lib.check(L.pmi_average_apply_dev(
+                _dptr(d_x), _dptr(d_y), _dptr(groups.rows), _dptr(groups.start), n, G, n_pixel, ov, _dptr(self.d_cos),
+                _dptr(self.d_sin), self.n_angles, _dptr(parts), chunks, _dptr(choice), _dptr(x_out), _dptr(y_out), stream),
+                "pmi_average_apply_dev"))
+            return {"image": host_image, "choice": choice.cpu().numpy().reshape(G, 3), "x": x_out.cpu().numpy(),
+                    "y": y_out.cpu().numpy(), "chunks": chunks, "ms": ms}

@@ -825,7 +825,7 @@ def _reference_module(given, name: str):
 
 def install(picasso_localize=None, picasso_gaussmle=None, picasso_gausslq=None, picasso_zfit=None,
             picasso_render=None, picasso_imageprocess=None, picasso_postprocess=None, *, fused: bool = False,
-            devices=None, picasso_aim=None, picasso_clusterer=None, picasso_spinna=None) -> None:
+            devices=None, picasso_aim=None, picasso_clusterer=None, picasso_spinna=None, picasso_average=None) -> None:
     """Rebind the reference package's hot-path functions to this backend, so that
     picasso.__main__ and the GUI run on the GPU unchanged.  Modules not given are taken
     from the installed ``picasso`` package; the rows next to the path (z fit, render, RCC undrift) are rebound
@@ -847,7 +847,9 @@ def install(picasso_localize=None, picasso_gaussmle=None, picasso_gausslq=None, 
     ``picasso.postprocess`` also gets the nearest-neighbour distances (``postprocess.NN_NAMES``: ``nn_analysis``), and
     ``picasso_spinna``, when given, ``get_NN_dist``: the rest of SPINNA stays its own and calls it; and the cluster
     combine (``postprocess.COMBINE_NAMES``: ``cluster_combine``, ``cluster_combine_dist``), which
-    `picasso cluster_combine` and `picasso cluster_combine_dist` call."""
+    `picasso cluster_combine` and `picasso cluster_combine_dist` call.
+    ``picasso_average``, when given, gets the particle averaging (``average.AVERAGE_NAMES``: ``average`` and the helpers
+    beside it), which `picasso average` and the Average GUI call."""
     if picasso_localize is None:
         import picasso.localize as picasso_localize       # the installed reference
     if picasso_gaussmle is None:
@@ -918,3 +920,7 @@ def install(picasso_localize=None, picasso_gaussmle=None, picasso_gausslq=None, 
         from . import spinna as amd_spinna
         for name in amd_spinna.SPINNA_NAMES:
             setattr(picasso_spinna, name, getattr(amd_spinna, name))
+    if picasso_average is not None:
+        from . import average as amd_average
+        for name in amd_average.AVERAGE_NAMES:
+            setattr(picasso_average, name, getattr(amd_average, name))
