@@ -66,6 +66,8 @@
  *                      (:1002-1055 distance_histogram, :1505-1540 pair_correlation)
  *   pmi_knn_*          picasso/postprocess.py:3704-3739 nn_analysis, picasso/spinna.py:696-747
  *                      get_NN_dist (scipy.spatial.KDTree(X2).query(X1, k))
+ *   pmi_frc_*, pmi_radial_sum  picasso/postprocess.py:1398-1502 _frc (from the two rendered histograms to the curve),
+ *                      picasso/masking.py:649-671 threshold_tukey, picasso/imageprocess.py:283-321 radial_sum
  */
 #ifndef PICASSO_HIP_H
 #define PICASSO_HIP_H
@@ -856,6 +858,35 @@ int pmi_average_apply_dev(const float *d_x, const float *d_y, const int32_t *d_r
                           int64_t n_groups, int64_t n_pixel, double oversampling, const double *d_cos, const double *d_sin,
                           int64_t n_angles, const int32_t *d_parts, int64_t chunks, int32_t *d_choice, float *d_x_out,
                           float *d_y_out, void *stream);
+
+/* ---- Fourier ring correlation (picasso/postprocess.py:1398-1502 _frc, picasso/imageprocess.py:283-321 radial_sum, ------- *
+ *      csrc/frc.hip, csrc/frc_core.h)
+ * pmi_frc_curve[_dev]    im1, im2: two float32 images of side m, row-major.  An even m loses its last row and column
+ *                        (n = m - 1), an odd one keeps all (n = m).  w: the n float64 values of the Tukey profile
+ *                        (threshold_tukey's one row, computed by the caller with NumPy's cos).  Outputs, with
+ *                        rings = n / 2 + 1: masked1 / masked2 (n x n float32) = float32(float64(im) * (w[j] * w[n - 1 - i])),
+ *                        NumPy's bits for `im *= mask`; sums (3 x rings float64) = the ring sums of real(F1 conj F2),
+ *                        |F1|^2, |F2|^2 over the whole fftshifted plane, F the float64 transforms of the masked images;
+ *                        curve (rings float64) = sums[0] / sqrt(|sums[1] * sums[2]|), NaN -> 0.  Ring r holds the bins
+ *                        with r^2 <= kx^2 + ky^2 < (r + 1)^2 in integer arithmetic; the corners beyond ring n / 2 are
+ *                        dropped.  Deterministic: no atomics, a fixed order of additions.  The _dev variant takes device
+ *                        pointers, runs on `stream`, synchronises it, and fills ms4 (host, may be NULL) with the
+ *                        milliseconds of window, transforms, ring sums and curve by device events.
+ * pmi_radial_sum         host arrays: out[r] = the sum of the bins of ring r of a centred n x n image (n odd), summed in
+ *                        float64 per component and cast to the image's type (PMI_RADIAL_*).
+ * PMI_FRC_MAX_SIDE       the largest odd side: kx^2 + ky^2 stays below 2^28, and the two float64 images and two half
+ *                        spectra take 32 n^2 bytes of scratch (8.6 GB) beside hipFFT's own work area.              */
+#define PMI_FRC_MAX_SIDE 16385
+#define PMI_RADIAL_F32 0
+#define PMI_RADIAL_F64 1
+#define PMI_RADIAL_C64 2
+#define PMI_RADIAL_C128 3
+int pmi_frc_max_side(void);
+int pmi_frc_curve(const float *im1, const float *im2, int64_t m, const double *w, double *sums, double *curve,
+                  float *masked1, float *masked2);
+int pmi_frc_curve_dev(const float *d_im1, const float *d_im2, int64_t m, const double *d_w, double *d_sums, double *d_curve,
+                      float *d_masked1, float *d_masked2, float *ms4, void *stream);
+int pmi_radial_sum(const void *image, int dtype, int64_t n, void *out);
 
 /* ---- timing hooks for bench.py (HIP events on the given stream) ------- */
 int pmi_event_create(void **event);

@@ -147,6 +147,10 @@ SYMBOLS = {
     "pmi_average_align_dev": (_i32, [_p, _p, _p, _p, _i64, _i64, _i64, _f64, _f64, _f64, _p, _p, _i64, _i64, _p, _i32, _p,
                                      _p, _p]),
     "pmi_average_apply_dev": (_i32, [_p, _p, _p, _p, _i64, _i64, _i64, _f64, _p, _p, _i64, _p, _i64, _p, _p, _p, _p]),
+    "pmi_frc_max_side": (_i32, []),
+    "pmi_frc_curve": (_i32, [_p, _p, _i64, _p, _p, _p, _p, _p]),
+    "pmi_frc_curve_dev": (_i32, [_p, _p, _i64, _p, _p, _p, _p, _p, _p, _p]),
+    "pmi_radial_sum": (_i32, [_p, _i32, _i64, _p]),
     "pmi_event_create": (_i32, [_p]),
     "pmi_event_record": (_i32, [_p, _p]),
     "pmi_event_elapsed_ms": (_i32, [_p, _p, _p]),

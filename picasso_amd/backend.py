@@ -1655,3 +1655,109 @@ class AverageAligner:
                 "pmi_average_apply_dev"))
             return {"image": host_image, "choice": choice.cpu().numpy().reshape(G, 3), "x": x_out.cpu().numpy(),
                     "y": y_out.cpu().numpy(), "chunks": chunks, "ms": ms}
+
+
+# ---- Fourier ring correlation and radial sums (csrc/frc.hip, picasso/postprocess.py:1398-1502, imageprocess.py:283-321) ----
+FRC_MAX_SIDE = 16385               # PMI_FRC_MAX_SIDE: the largest odd image side
+FRC_BLOCK = 256                    # lanes of a ring's workgroup: a ring of at most that many row segments gives each lane one
+RADIAL_TYPES = {np.dtype("float32"): 0, np.dtype("float64"): 1, np.dtype("complex64"): 2, np.dtype("complex128"): 3}
+
+
+def frc_max_side() -> int:
+    """FRC_MAX_SIDE as the loaded library has it; a library built with another bound is refused."""
+    side = int(_lib.load().pmi_frc_max_side())
+    if side != FRC_MAX_SIDE:
+        raise _lib.HipBackendError(f"libpicasso_hip was built with an FRC side of {side}, this package with {FRC_MAX_SIDE}")
+    return side
+
+
+def _frc_side(m: int) -> int:
+    n = m if m % 2 else m - 1
+    if n < 1:
+        raise ValueError(f"an image of side {m} leaves nothing after the crop to an odd side")
+    if n > frc_max_side():
+        raise MemoryError(f"an FRC image of side {n} exceeds the limit of {FRC_MAX_SIDE}: two float64 images and two "
+                          f"half spectra of that side would take {32 * n * n / 2 ** 30:.0f} GiB of device memory")
+    return n
+
+
+def render_hist_device(x, y, oversampling, y_min, x_min, y_max, x_max):
+    """The histogram render (``render_arrays`` without widths) that stays on the device -> (n, float32 device tensor)."""
+    import torch
+    _lib.require_gpu()
+    L = _lib.load()
+    ny, nx = ctypes.c_int64(), ctypes.c_int64()
+    _lib.check(L.pmi_render_dims(float(oversampling), float(y_min), float(x_min), float(y_max), float(x_max),
+                                 ctypes.byref(ny), ctypes.byref(nx)), "pmi_render_dims")
+    if ny.value <= 0 or nx.value <= 0:
+        raise ValueError("empty viewport")
+    if max(ny.value, nx.value) > FRC_MAX_SIDE + 1:
+        raise MemoryError(f"a render of {ny.value} x {nx.value} pixels exceeds the FRC limit of {FRC_MAX_SIDE} per side")
+    d_x, d_y = _to_device(x, np.float32), _to_device(y, np.float32)
+    image = torch.empty((ny.value, nx.value), dtype=torch.float32, device=d_x.device)
+    count = torch.zeros(1, dtype=torch.int64, device=d_x.device)
+    with _lib.lock():
+        _lib.check(L.pmi_render_hist_dev(_dptr(d_x), _dptr(d_y), len(d_x), float(oversampling), float(y_min), float(x_min),
+                                         float(y_max), float(x_max), _dptr(image), ny.value, nx.value, _dptr(count), None),
+                   "pmi_render_hist_dev")
+        n = int(count.cpu()[0])
+    return n, image
+
+
+def frc_arrays(im1, im2, w):
+    """The device part of ``_frc``: two square float32 images of one side m (NumPy arrays, or device tensors as
+    ``render_hist_device`` returns them) and the float64 Tukey profile ``w`` of the odd side n (m, or m - 1 for an even
+    m) -> dict with ``images`` (the two masked float32 images, n x n, NumPy's bits for ``im *= mask``), ``sums``
+    (3 x rings float64: numerator, power 1, power 2), ``curve`` (rings float64, NaN -> 0) and ``ms`` (window, fft, rings,
+    curve: milliseconds by device events)."""
+    import torch
+    _lib.require_gpu()
+    L = _lib.load()
+    if tuple(im1.shape) != tuple(im2.shape) or len(im1.shape) != 2 or im1.shape[0] != im1.shape[1]:
+        raise ValueError(f"two square images of one side are needed, not {tuple(im1.shape)} and {tuple(im2.shape)}")
+    m = int(im1.shape[0])
+    n = _frc_side(m)
+    w = np.ascontiguousarray(w, np.float64)
+    if w.shape != (n,):
+        raise ValueError(f"the window profile must have the {n} values of the odd side, not {w.shape}")
+
+    def dev(im):
+        if isinstance(im, torch.Tensor):
+            if im.dtype != torch.float32 or not im.is_cuda:
+                raise TypeError("a device image must be a float32 tensor on the GPU")
+            return im.contiguous()
+        im = np.asarray(im)
+        if im.dtype != np.float32:
+            raise TypeError(f"the images must be float32, not {im.dtype}")
+        return _to_device(im)
+
+    d1, d2, d_w = dev(im1), dev(im2), _to_device(w)
+    rings = n // 2 + 1
+    sums = torch.empty(3 * rings, dtype=torch.float64, device=d1.device)
+    curve = torch.empty(rings, dtype=torch.float64, device=d1.device)
+    m1 = torch.empty((n, n), dtype=torch.float32, device=d1.device)
+    m2 = torch.empty_like(m1)
+    ms = (ctypes.c_float * 4)()
+    torch.cuda.current_stream().synchronize()
+    with _lib.lock():
+        _lib.check(L.pmi_frc_curve_dev(_dptr(d1), _dptr(d2), m, _dptr(d_w), _dptr(sums), _dptr(curve), _dptr(m1), _dptr(m2),
+                                       ctypes.cast(ms, ctypes.c_void_p), None), "pmi_frc_curve_dev")
+    return {"images": (m1.cpu().numpy(), m2.cpu().numpy()), "sums": sums.cpu().numpy().reshape(3, rings),
+            "curve": curve.cpu().numpy(), "ms": dict(zip(("window", "fft", "rings", "curve"), (float(v) for v in ms)))}
+
+
+def radial_sum_array(image) -> np.ndarray:
+    """Ring sums of a centred square image of odd side: float32 / float64 / complex64 / complex128, summed in float64
+    per component and cast to the image's type."""
+    image = np.ascontiguousarray(image)
+    if image.ndim != 2 or image.shape[0] != image.shape[1] or image.shape[0] % 2 != 1:
+        raise ValueError(f"a square image of odd side is needed, not {image.shape}")
+    if image.dtype not in RADIAL_TYPES:
+        raise TypeError(f"radial sums of {image.dtype} images are not built (float32, float64, complex64, complex128)")
+    n = _frc_side(int(image.shape[0]))
+    _lib.require_gpu()
+    out = np.empty(n // 2 + 1, image.dtype)
+    with _lib.lock():
+        rc = _lib.load().pmi_radial_sum(_lib.ptr(image), RADIAL_TYPES[image.dtype], n, _lib.ptr(out))
+    _lib.check(rc, "pmi_radial_sum")
+    return out

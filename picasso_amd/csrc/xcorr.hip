@@ -52,6 +52,10 @@ static int get_plans(int64_t Y, int64_t X, Plans *out)
     return PMI_OK;
 }
 
+// forward plans of callers that never transform back (frc.hip): the pair above when it exists, else a plan of its own,
+// so that an odd or prime side does not pay for an inverse plan nobody executes
+static std::map<std::tuple<int, int64_t, int64_t>, hipfftHandle> g_forward;
+
 // sums[i] != 0 when image i is not empty (picasso/imageprocess.py:85-86 tests np.sum(image) == 0; the
 // images are non-negative renders, so that is "all pixels zero").  grid = (chunks, images); every block
 // adds the float64 sum of its chunk of non-negative magnitudes to the image's total.
@@ -142,11 +146,34 @@ __global__ __launch_bounds__(256) void peak_kernel(const double *__restrict__ r,
 
 }  // namespace xc
 
+int fft_forward_plan(int64_t Y, int64_t X, hipfftHandle *fwd)
+{
+    std::lock_guard<std::mutex> lk(xc::g_plans_mu);
+    int dev = 0;
+    PMI_HIP(hipGetDevice(&dev));
+    const auto key = std::make_tuple(dev, Y, X);
+    const auto pair = xc::g_plans.find(key);
+    if (pair != xc::g_plans.end()) { *fwd = pair->second.fwd; return PMI_OK; }
+    auto it = xc::g_forward.find(key);
+    if (it == xc::g_forward.end()) {
+        hipfftHandle p;
+        if (hipfftPlan2d(&p, (int)Y, (int)X, HIPFFT_D2Z) != HIPFFT_SUCCESS) {
+            set_error("hipfftPlan2d(%lld, %lld) failed", (long long)Y, (long long)X);
+            return PMI_ERR_HIP;
+        }
+        it = xc::g_forward.emplace(key, p).first;
+    }
+    *fwd = it->second;
+    return PMI_OK;
+}
+
 void release_fft_plans()
 {
     std::lock_guard<std::mutex> lk(xc::g_plans_mu);
     for (auto &kv : xc::g_plans) { hipfftDestroy(kv.second.fwd); hipfftDestroy(kv.second.inv); }
     xc::g_plans.clear();
+    for (auto &kv : xc::g_forward) hipfftDestroy(kv.second);
+    xc::g_forward.clear();
 }
 
 }  // namespace pmi

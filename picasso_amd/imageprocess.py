@@ -55,3 +55,14 @@ def rcc(segments, max_shift: float | None = None, callback=None):
             if callback is not None:
                 callback(flag)
     return lib.minimize_shifts(shifts_x, shifts_y)
+
+
+def radial_sum(image):
+    """Radial projection of the sum of pixel values (imageprocess.py:283-321): the sum of all pixels at a distance r
+    from the centre with n <= r < n + 1 is stored at position n.  One pass per ring on the device (csrc/frc.hip) instead
+    of one full-image mask per radius; the sums are taken in float64 and cast to the image's type."""
+    image = np.asarray(image)
+    assert image.ndim == 2, "Input image must be 2D."
+    assert image.shape[0] == image.shape[1], "Input image must be square."
+    assert image.shape[0] % 2 == 1, "Input image size must be odd."
+    return backend.radial_sum_array(image)

@@ -847,7 +847,9 @@ def install(picasso_localize=None, picasso_gaussmle=None, picasso_gausslq=None, 
     ``picasso.postprocess`` also gets the nearest-neighbour distances (``postprocess.NN_NAMES``: ``nn_analysis``), and
     ``picasso_spinna``, when given, ``get_NN_dist``: the rest of SPINNA stays its own and calls it; and the cluster
     combine (``postprocess.COMBINE_NAMES``: ``cluster_combine``, ``cluster_combine_dist``), which
-    `picasso cluster_combine` and `picasso cluster_combine_dist` call.
+    `picasso cluster_combine` and `picasso cluster_combine_dist` call; and the Fourier ring correlation
+    (``postprocess.FRC_NAMES``: ``frc``, ``_frc``) with ``picasso.imageprocess.radial_sum`` under it, which Render's
+    resolution box calls (``plot_frc`` stays the reference's own).
     ``picasso_average``, when given, gets the particle averaging (``average.AVERAGE_NAMES``: ``average`` and the helpers
     beside it), which `picasso average` and the Average GUI call."""
     if picasso_localize is None:
@@ -899,12 +901,12 @@ def install(picasso_localize=None, picasso_gaussmle=None, picasso_gausslq=None, 
     picasso_imageprocess = _reference_module(picasso_imageprocess, "imageprocess")
     if picasso_imageprocess is not None:
         from . import imageprocess as amd_ip
-        for name in ("xcorr", "get_image_shift", "rcc"):
+        for name in ("xcorr", "get_image_shift", "rcc", "radial_sum"):
             setattr(picasso_imageprocess, name, getattr(amd_ip, name))
     picasso_postprocess = _reference_module(picasso_postprocess, "postprocess")
     if picasso_postprocess is not None:
         from . import postprocess as amd_pp
-        for name in ("segment", "undrift") + amd_pp.LINK_NENA_NAMES + amd_pp.PAIR_NAMES + amd_pp.KINETICS_NAMES + amd_pp.NN_NAMES + amd_pp.COMBINE_NAMES:
+        for name in ("segment", "undrift") + amd_pp.LINK_NENA_NAMES + amd_pp.PAIR_NAMES + amd_pp.KINETICS_NAMES + amd_pp.NN_NAMES + amd_pp.COMBINE_NAMES + amd_pp.FRC_NAMES:
             setattr(picasso_postprocess, name, getattr(amd_pp, name))
     picasso_aim = _reference_module(picasso_aim, "aim")
     if picasso_aim is not None:

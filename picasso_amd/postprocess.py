@@ -729,3 +729,112 @@ def cluster_combine_dist(locs: pd.DataFrame, pixelsize: float | None = None) -> 
         if three:
             out["mind_dist_xy"] = min_dist_xy.astype(np.float32)
     return pd.DataFrame(out)
+
+
+# ---- Fourier ring correlation (postprocess.py:1320-1502) ----------------------------------------------------------
+FRC_NAMES = ("frc", "_frc")
+
+
+def frc(locs: pd.DataFrame, info, viewport, *, random_seed: int = 42) -> dict:
+    """Fourier ring correlation resolution (postprocess.py:1320-1395; Nieuwenhuizen et al., Nat. Methods 10, 557-562).
+    -> dict with "frc_curve", "frc_curve_smooth", "frequencies" (nm^-1), "resolution" (nm, or None) and "images" (the
+    two rendered and masked half-data images).  The split uses NumPy's legacy global generator, as the reference does:
+    it is part of the result."""
+    pixelsize = lib.get_from_metadata(info, "Pixelsize", raise_error=True)
+    lp = nena(locs, info)[1]
+    # correct for the viewport to be square
+    viewport_width = viewport[1][1] - viewport[0][1]
+    viewport_height = viewport[1][0] - viewport[0][0]
+    if viewport_width < viewport_height:
+        y_center = 0.5 * (viewport[0][0] + viewport[1][0])
+        y_min = y_center - viewport_width / 2
+        y_max = y_center + viewport_width / 2
+        viewport = ((y_min, viewport[0][1]), (y_max, viewport[1][1]))
+    elif viewport_height < viewport_width:
+        x_center = 0.5 * (viewport[0][1] + viewport[1][1])
+        x_min = x_center - viewport_height / 2
+        x_max = x_center + viewport_height / 2
+        viewport = ((viewport[0][0], x_min), (viewport[1][0], x_max))
+
+    # select the locs within the viewport
+    (y_min, x_min), (y_max, x_max) = viewport
+    in_view = (locs["x"] > x_min) & (locs["y"] > y_min) & (locs["x"] < x_max) & (locs["y"] < y_max)
+    locs = locs.loc[in_view]
+
+    np.random.seed(random_seed)
+    # split locs randomly into two halves
+    r_idx = np.random.permutation(len(locs))
+    locs1 = locs.iloc[r_idx[: len(r_idx) // 2]]
+    locs2 = locs.iloc[r_idx[len(r_idx) // 2:]]
+    frc_curve, frc_curve_smooth, frequencies, resolution, images = _frc(locs1, locs2, pixelsize, lp, viewport)
+    return {"frc_curve": frc_curve, "frc_curve_smooth": frc_curve_smooth, "frequencies": frequencies,
+            "resolution": resolution, "images": images}
+
+
+def _frc_render(locs, info, oversampling, viewport):
+    """``render.render(locs, info, oversampling, viewport, None)[1]`` with the image left on the device: the head of
+    ``render.render`` expression for expression (the deprecated positional oversampling goes through the display pixel
+    size and back), then the histogram kernel."""
+    pixelsize = lib.get_from_metadata(info, "Pixelsize", raise_error=True)
+    lib.deprecation_warning("Deprecation warning: the 'oversampling' parameter is deprecated and will be removed "
+                            "in v0.11.0. Use 'disp_px_size' instead.")
+    disp_px_size = pixelsize / oversampling
+    oversampling = pixelsize / disp_px_size
+    (y_min, x_min), (y_max, x_max) = viewport
+    return backend.render_hist_device(locs["x"].to_numpy(), locs["y"].to_numpy(), oversampling, y_min, x_min, y_max, x_max)[1]
+
+
+def _frc_curve(im1, im2):
+    """Two square float32 renders of one side (host or device) -> (curve, (masked image 1, masked image 2), details):
+    the crop to an odd side, the Tukey window, the two transforms and the ring sums on the device (csrc/frc.hip).  The
+    curve is float64: the device transforms in double precision where the reference's ``np.fft.fft2`` of a float32
+    image works in single."""
+    from . import masking
+    m = int(im1.shape[0])
+    w = masking.tukey_profile(m if m % 2 else m - 1)
+    out = backend.frc_arrays(im1, im2, w)
+    return out["curve"], out["images"], out
+
+
+def _fire_resolution(frequencies, smooth, threshold: float = 1 / 7):
+    """The first crossing of the smoothed curve below the threshold, linearly interpolated -> resolution in nm, or None
+    (postprocess.py:1487-1501)."""
+    resolution = None
+    for i in range(1, len(smooth)):
+        if smooth[i - 1] >= threshold and smooth[i] < threshold:
+            # linear interpolation
+            f1 = frequencies[i - 1]
+            f2 = frequencies[i]
+            r1 = smooth[i - 1]
+            r2 = smooth[i]
+            f_res = f1 + (threshold - r1) * (f2 - f1) / (r2 - r1)
+            resolution = 1 / f_res  # in nm
+            break
+    return resolution
+
+
+def _frc(locs1: pd.DataFrame, locs2: pd.DataFrame, pixelsize: float, lp: float, viewport):
+    """One FRC curve and its resolution at the 1/7 threshold (postprocess.py:1398-1502) -> (frc_curve,
+    frc_curve_smooth, frequencies, resolution, (image 1, image 2)).  The renders, the window, the transforms and the
+    ring sums stay on the device; the masked images and the curve come back.  The smoothing is statsmodels' LOESS on
+    the host (``masking.loess_smooth``)."""
+    from . import masking
+    # render images
+    binsize = lp / 2
+    oversampling = 1 / binsize
+    dummy_info = {"Pixelsize": pixelsize}
+    im1 = _frc_render(locs1, dummy_info, oversampling, viewport)
+    im2 = _frc_render(locs2, dummy_info, oversampling, viewport)
+    if im1.shape[0] != im1.shape[1]:
+        raise AssertionError("Image must be square")          # threshold_tukey's assertion (masking.py:662)
+    frc_curve, images, _ = _frc_curve(im1, im2)
+    side = images[0].shape[0]
+
+    # smooth the frc curve
+    sspan = max(int(np.ceil(int(side / 2) / 20)), 5)
+    frc_curve_smooth = masking.loess_smooth(frc_curve, sspan)
+
+    # find the frequencies (q) and resolution
+    frequencies = np.arange(len(frc_curve)) / side / (pixelsize * binsize)
+    resolution = _fire_resolution(frequencies, frc_curve_smooth)
+    return frc_curve, frc_curve_smooth, frequencies, resolution, images
