@@ -202,11 +202,24 @@ __device__ __forceinline__ float np_maxf(float a, float b) { return (a != a) ? a
 __device__ __forceinline__ float np_minf(float a, float b) { return (a != a) ? a : ((b != b) ? b : (a < b ? a : b)); }
 __device__ __forceinline__ float np_signf(float a) { return (a != a) ? a : (a > 0.f ? 1.f : (a < 0.f ? -1.f : 0.f)); }
 
+// E of one pixel for the Fisher / log-likelihood pass, from the values at its two boundaries a_lo < a_hi (arguments of erf):
+// e = erf(a), c = erfc(|a|).  erf(a_hi) - erf(a_lo) of two float32 values near +-1 is 2^-25 off in ABSOLUTE terms, which
+// on a far pixel of a bright spot over 1 - 2 photons of background puts N 2^-25 / bg of relative error into the model
+// and into that pixel's weight 1 / model (up to 2.4e-4 of the CRLB, tests/test_gpu_mle_fisher.py).  Where both boundaries lie
+// on one side of the centre, beyond 0.5, the difference of the complements is the same number without the cancellation.
+__device__ __forceinline__ bool pixel_tail(float a_lo, float a_hi) { return a_lo * a_hi > 0.f && fminf(fabsf(a_lo), fabsf(a_hi)) > 0.5f; }
+__device__ __forceinline__ float pixel_E(float a_lo, float a_hi, float e_lo, float e_hi, float c_lo, float c_hi)
+{
+    return pixel_tail(a_lo, a_hi) ? 0.5f * fabsf(c_lo - c_hi) : 0.5f * (e_hi - e_lo);
+}
+
 // One-dimensional pixel-integrated Gaussian terms for pixel index `i`:
 //   E   = deltaE                      (gaussmle.py:268-280)
 //   A   = dE/dmu,   A2 = d2E/dmu2     (gaussmle.py:283-303, without photons*PSF_other)
 //   S   = dE/dsig,  S2 = d2E/dsig2    (gaussmle.py:306-336)
+// FINAL: the Fisher / log-likelihood pass, E from pixel_E; the Newton loop keeps the arithmetic its results are pinned to
 struct Terms { float E, A, A2, S, S2; };
+template <bool FINAL = false>
 __device__ __forceinline__ Terms gauss_terms(float i, float mu, float sigma)
 {
     const float is = 1.0f / sigma;
@@ -215,7 +228,9 @@ __device__ __forceinline__ Terms gauss_terms(float i, float mu, float sigma)
     const float is2 = is * is;
     const float dm = i - mu - 0.5f, dp = i - mu + 0.5f;
     Terms t;
-    t.E = 0.5f * (erff(dp * sn) - erff(dm * sn));
+    const float a_lo = dm * sn, a_hi = dp * sn;
+    if (FINAL && pixel_tail(a_lo, a_hi)) t.E = 0.5f * fabsf(erfcf(fabsf(a_lo)) - erfcf(fabsf(a_hi)));
+    else t.E = 0.5f * (erff(a_hi) - erff(a_lo));
     const float gm = __expf(-0.5f * dm * dm * is2), gp = __expf(-0.5f * dp * dp * is2);
     const float q1 = dm * gm - dp * gp;
     const float q3 = dm * dm * dm * gm - dp * dp * dp * gp;

@@ -272,8 +272,8 @@ __global__ __launch_bounds__(FIT_NT) void mle_fit_kernel(FitParams p, int stages
             const float sgy = NP == 6 ? th[5] : th[4];
 #pragma unroll
             for (int s = 0; s < PPL; s++) {
-                Terms tx = gauss_terms((float)pi[s], th[0], th[4]);
-                Terms ty = gauss_terms((float)pj[s], th[1], sgy);
+                Terms tx = gauss_terms<true>((float)pi[s], th[0], th[4]);
+                Terms ty = gauss_terms<true>((float)pj[s], th[1], sgy);
                 const float N_ = th[2];
                 float du[6];
                 du[0] = N_ * ty.E * tx.A;
@@ -447,7 +447,8 @@ __global__ __launch_bounds__(256) void crlb_kernel(const double *__restrict__ fi
         }
     }
     // (one reciprocal per pivot instead of a division per entry — 6 float64 divisions instead of 36; the results go to
-    // float32, and are compared with the reference's pinv at 2e-3)
+    // float32, and are compared with a float64 inverse at the device's own theta, row by row, at MARGIN K_ref u + 2^-23 with
+    // u = NP 2^-24 / lambda_min(C): tests/test_gpu_mle_fisher.py)
     double L[36], D[6], rD[6], diag[6];
     bool bad = false;
     double trM = 0.0;

@@ -130,7 +130,9 @@ __device__ __forceinline__ float max_np(float a, float b) { const float c = fmax
 __device__ __forceinline__ float min_np(float a, float b) { const float c = fminf(a, b); return (a != a) ? a : c; }
 
 struct BTerms { float E, A, A2, S, S2; };
-// per-pixel terms of index j from the boundary values of lane j (k = j) and lane j+1
+// per-pixel terms of index j from the boundary values of lane j (k = j) and lane j+1.  FINAL (the Fisher / log-likelihood
+// pass): E from pixel_E (fit_common.h), one erfc per boundary more; the Newton loop keeps the arithmetic its results are pinned to
+template <bool FINAL = false>
 __device__ __forceinline__ BTerms boundary_terms(float jf, float mu, float sigma)
 {
     const float is = rcp_f32(sigma);
@@ -143,7 +145,10 @@ __device__ __forceinline__ BTerms boundary_terms(float jf, float mu, float sigma
     const float q1 = u0 * g0 - u1 * g1;
     const float q3 = u0 * u0 * u0 * g0 - u1 * u1 * u1 * g1;
     BTerms t;
-    t.E = 0.5f * (e1 - e0);
+    if (FINAL) {
+        const float c0 = erfcf(fabsf(u0 * sn));
+        t.E = pixel_E(u0 * sn, u1 * sn, e0, e1, c0, from_next(c0));
+    } else t.E = 0.5f * (e1 - e0);
     t.A = (g0 - g1) * c1;
     t.A2 = q1 * c1 * is2;
     t.S = q1 * c1 * is;
@@ -824,8 +829,8 @@ __global__ __launch_bounds__(FIT_NT) void g8_final_kernel(FitParams p)
     double *red = &s_x[wid][g][0];
     float *cols = reinterpret_cast<float *>(red);
     const float sgy = NP == 6 ? th[5] : th[4];
-    const BTerms tx = boundary_terms(jf, th[0], th[4]);
-    const BTerms ty = boundary_terms(jf, th[1], sgy);
+    const BTerms tx = boundary_terms<true>(jf, th[0], th[4]);
+    const BTerms ty = boundary_terms<true>(jf, th[1], sgy);
     {
         // column j: (AA, AE, A, AS | EE, E, ES, 1 | S, SS, -, -)
         float4 *c = reinterpret_cast<float4 *>(cols + j * 12);
