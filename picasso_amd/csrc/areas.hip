@@ -25,7 +25,7 @@
 //
 // Every loop is bounded by the rows of the group, the bins of the image or a constant; every index into the image is
 // below its bins, which the kernel checks against LDS or against the scratch it was given.  No contraction.
-#include "rows_common.h"
+#include "rows_groups.h"
 
 #pragma clang fp contract(off)
 
@@ -38,16 +38,6 @@ constexpr int LDS_BINS = PMI_AREAS_LDS_BINS;
 constexpr int RADIUS = 8;
 constexpr int OTSU_BINS = 256;
 static_assert(BLOCK == OTSU_BINS, "lane t clears bin t of the Otsu histogram");
-
-__device__ __forceinline__ bool row_ok(int32_t i, int32_t n) { return (uint32_t)i < (uint32_t)n; }
-
-// [a, b) of group g; an inconsistent start table gives an empty run, never a read out of bounds
-__device__ __forceinline__ void run_of(const int32_t *__restrict__ start, int32_t g, int32_t n, int32_t *a, int32_t *b)
-{
-    *a = start[g];
-    *b = start[g + 1];
-    if (*a < 0 || *b > n || *a > *b) *a = *b = 0;
-}
 
 // coordinate d of row i in the points' common type, as float64
 __device__ __forceinline__ double coord(const pmi_areas_columns &c, int d, int32_t i)
@@ -316,10 +306,8 @@ __global__ __launch_bounds__(BLOCK) void image_kernel(pmi_areas_columns c, const
 static int check(const char *what, const pmi_areas_columns *cols, const int32_t *d_rows, const int32_t *d_start, int64_t n,
                  int64_t n_groups)
 {
-    if (n < 0 || n > INT32_MAX - 1 || n_groups < 0 || n_groups > n) {
-        set_error("%s: %lld rows, %lld groups (rows are indexed with int32)", what, (long long)n, (long long)n_groups);
-        return PMI_ERR_ARG;
-    }
+    const int rc = check_rows(what, n, n_groups, "groups");
+    if (rc) return rc;
     if (!cols || (cols->dims != 2 && cols->dims != 3) || (n > 0 && (!d_rows || !d_start))) {
         set_error("%s: 2 or 3 dimensions, and no NULL table", what);
         return PMI_ERR_ARG;

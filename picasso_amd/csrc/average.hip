@@ -18,7 +18,7 @@
 //
 // Every loop is bounded by the rows of the group, the pixels of the image or the angles of the chunk; every index into
 // the image is below n * n (average_core.h), every index into the list below PMI_AVERAGE_LIST.  No contraction.
-#include "rows_common.h"
+#include "rows_groups.h"
 #include "average_core.h"
 
 #pragma clang fp contract(off)
@@ -33,16 +33,6 @@ constexpr int SMALL_BINS = 4096;      // the usual image (28 x 28 at the default
 constexpr int LIST = PMI_AVERAGE_LIST;
 static_assert(PMI_AVERAGE_MAX_PIXELS <= 32768, "a pixel index must fit 16 bits, n * n an int32");
 static_assert(2 * (4 * LDS_BINS + 4 * LIST + 4 * 1024) <= 160 * 1024, "two workgroups of the LDS path per CU");
-
-__device__ __forceinline__ bool row_ok(int32_t i, int32_t n) { return (uint32_t)i < (uint32_t)n; }
-
-// [a, b) of group g; an inconsistent start table gives an empty run, never a read out of bounds
-__device__ __forceinline__ void run_of(const int32_t *__restrict__ start, int32_t g, int32_t n, int32_t *a, int32_t *b)
-{
-    *a = start[g];
-    *b = start[g + 1];
-    if (*a < 0 || *b > n || *a > *b) *a = *b = 0;
-}
 
 __global__ __launch_bounds__(BLOCK) void image_kernel(const float *__restrict__ x, const float *__restrict__ y,
                                                       int32_t n_rows, Geom geom, int32_t *__restrict__ image,

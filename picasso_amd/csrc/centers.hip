@@ -25,7 +25,8 @@
 // Every loop is bounded by the row count; no float atomics.
 #include <algorithm>
 
-#include "rows_common.h"
+#include "rows_groups.h"
+#include "segment_stats.h"
 
 #pragma clang fp contract(off)
 
@@ -33,33 +34,11 @@ namespace pmi {
 namespace centers {
 
 using namespace rows;
+using segstats::quiet_nan;
 
 constexpr int MAX_COLS = 32;
 
-template <typename T> __device__ __forceinline__ T quiet_nan();
-template <> __device__ __forceinline__ float quiet_nan<float>() { return __builtin_nanf(""); }
-template <> __device__ __forceinline__ double quiet_nan<double>() { return __builtin_nan(""); }
-
-// [a, b) of label g; an inconsistent start table gives an empty run, never a read out of bounds
-__device__ __forceinline__ void run_of(const int32_t *__restrict__ start, int32_t g, int32_t n, int32_t *a, int32_t *b)
-{
-    *a = start[g];
-    *b = start[g + 1];
-    if (*a < 0 || *b > n || *a > *b) *a = *b = 0;
-}
-
-__device__ __forceinline__ bool row_ok(int32_t i, int32_t n) { return (uint32_t)i < (uint32_t)n; }
-
 // ---- order -----------------------------------------------------------------------------------------------------
-__global__ void key_kernel(const int64_t *__restrict__ group, int32_t n, uint64_t g_min, uint64_t *__restrict__ keys,
-                           int32_t *__restrict__ rows)
-{
-    const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n) return;
-    keys[i] = (uint64_t)group[i] - g_min;
-    rows[i] = (int32_t)i;
-}
-
 __global__ void flag_kernel(const uint64_t *__restrict__ keys, int32_t n, uint32_t *__restrict__ flag)
 {
     const int64_t p = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
@@ -75,22 +54,9 @@ __global__ void start_kernel(const uint64_t *__restrict__ keys, const uint32_t *
     const int64_t p = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (p >= n) return;
     const uint32_t g = pos[p];
-    if (flag[p] && g < (uint32_t)n) {
-        start[g] = (int32_t)p;
-        unique[g] = (int64_t)(keys[p] + g_min);
-    }
-    if (p == n - 1) {
-        const uint32_t G = g + flag[p];
-        if (G <= (uint32_t)n) start[G] = n;
-        total[0] = G;
-    }
-}
-
-static int bits_of(uint64_t top)
-{
-    int bits = 1;
-    while (bits < 64 && (top >> bits)) bits++;
-    return bits;
+    const uint32_t G = close_runs(p, n, flag[p], g, (int32_t)p, n, start);
+    if (flag[p] && g < (uint32_t)n) unique[g] = (int64_t)(keys[p] + g_min);
+    if (p == n - 1) total[0] = G;
 }
 
 static int order(const int64_t *group, int32_t n, int64_t g_min, int64_t g_max, int32_t *rows_out, int32_t *start,
@@ -106,12 +72,10 @@ static int order(const int64_t *group, int32_t n, int64_t g_min, int64_t g_max, 
         flag = ar.take<uint32_t>(N), pos = ar.take<uint32_t>(N), total = ar.take<uint32_t>(1);
     });
     if (rc != PMI_OK) return rc;
-    const uint64_t lo = (uint64_t)g_min;
-    PMI_LAUNCH(key_kernel, n, s, group, n, lo, keys, rows);
-    if ((rc = sort_pairs(keys, keys_sorted, rows, rows_out, N, bits_of((uint64_t)g_max - lo), s)) != PMI_OK) return rc;
+    if ((rc = sort_by_column(group, g_min, g_max, true, keys, keys_sorted, rows, rows_out, n, s)) != PMI_OK) return rc;
     PMI_LAUNCH(flag_kernel, n, s, keys_sorted, n, flag);
     if ((rc = exclusive_scan_u32(flag, pos, N, s)) != PMI_OK) return rc;
-    PMI_LAUNCH(start_kernel, n, s, keys_sorted, flag, pos, n, lo, start, unique, total);
+    PMI_LAUNCH(start_kernel, n, s, keys_sorted, flag, pos, n, (uint64_t)g_min, start, unique, total);
     uint32_t h_total = 0;
     PMI_HIP(hipMemcpyAsync(&h_total, total, 4, hipMemcpyDeviceToHost, s));
     PMI_HIP(hipStreamSynchronize(s));
@@ -131,16 +95,6 @@ __global__ void weights_kernel(const T *__restrict__ lpx, const T *__restrict__ 
     if (i >= n) return;
     const T sum = lpx[i] + lpy[i];
     w[i] = (T)1 / (sum * sum);
-}
-
-// vs[p] = the value of sorted position p in the summing type A
-template <typename T, typename A>
-__global__ void gather_kernel(const T *__restrict__ data, const int32_t *__restrict__ rows, int32_t n, A *__restrict__ vs)
-{
-    const int64_t p = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (p >= n) return;
-    const int32_t i = rows[p];
-    vs[p] = row_ok(i, n) ? (A)data[i] : (A)0;
 }
 
 template <typename T, typename W, typename A>
@@ -233,10 +187,11 @@ static int chain(const A *vs, const int32_t *start, int32_t n, int32_t G, const 
     return PMI_OK;
 }
 
-template <typename T, typename A>
+template <typename T>
 static int mean_typed(const pmi_centers_column &c, const int32_t *rows, const int32_t *start, int32_t n, int32_t G,
                       void *buf, hipStream_t s)
 {
+    using A = typename Column<T>::sum_type;
     PMI_LAUNCH((gather_kernel<T, A>), n, s, (const T *)c.data, rows, n, (A *)buf);
     return chain<A>((const A *)buf, start, n, G, c, s);
 }
@@ -255,14 +210,9 @@ static int column(const pmi_centers_column &c, const int32_t *rows, const int32_
     const bool f32 = c.type == PMI_CENTERS_F32, w32 = c.w_type == PMI_CENTERS_F32;
     switch (c.op) {
     case PMI_CENTERS_MEAN:
-        switch (c.type) {
-        case PMI_CENTERS_F32: return mean_typed<float, float>(c, rows, start, n, G, buf, s);
-        case PMI_CENTERS_F64: return mean_typed<double, double>(c, rows, start, n, G, buf, s);
-        case PMI_CENTERS_U32: return mean_typed<uint32_t, double>(c, rows, start, n, G, buf, s);
-        case PMI_CENTERS_I32: return mean_typed<int32_t, double>(c, rows, start, n, G, buf, s);
-        case PMI_CENTERS_U64: return mean_typed<uint64_t, double>(c, rows, start, n, G, buf, s);
-        default: return mean_typed<int64_t, double>(c, rows, start, n, G, buf, s);
-        }
+        return with_column_type(c.type, [&](auto col) {
+            return mean_typed<typename decltype(col)::type>(c, rows, start, n, G, buf, s);
+        });
     case PMI_CENTERS_XSUM:
         if (f32 && w32) return xsum_typed<float, float, float>(c, rows, start, n, G, buf, s);
         if (f32) return xsum_typed<float, double, double>(c, rows, start, n, G, buf, s);
@@ -319,15 +269,6 @@ __global__ void coord_key_kernel(const T *__restrict__ v, const int32_t *__restr
     const int32_t i = rows ? rows[p] : (int32_t)p;
     keys[p] = row_ok(i, n) ? ordered_key((double)v[i]) : 0;
     if (rows_out) rows_out[p] = (int32_t)p;
-}
-
-__global__ void group_key_kernel(const int64_t *__restrict__ group, const int32_t *__restrict__ rows, int32_t n,
-                                 uint64_t g_min, uint64_t *__restrict__ keys)
-{
-    const int64_t p = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (p >= n) return;
-    const int32_t i = rows[p];
-    keys[p] = row_ok(i, n) ? (uint64_t)group[i] - g_min : 0;
 }
 
 template <typename TX, typename TY>
@@ -389,25 +330,14 @@ static int hull_typed(const TX *x, const TY *y, const int64_t *group, int64_t g_
         xs = ar.take<double>(N), ys = ar.take<double>(N);
     });
     if (rc != PMI_OK) return rc;
-    const uint64_t lo = (uint64_t)g_min;
     PMI_LAUNCH(coord_key_kernel<TY>, n, s, y, nullptr, n, keys, rows);
     if ((rc = sort_pairs(keys, keys_sorted, rows, rows_sorted, N, 64, s)) != PMI_OK) return rc;
     PMI_LAUNCH(coord_key_kernel<TX>, n, s, x, rows_sorted, n, keys, nullptr);
     if ((rc = sort_pairs(keys, keys_sorted, rows_sorted, rows, N, 64, s)) != PMI_OK) return rc;
-    PMI_LAUNCH(group_key_kernel, n, s, group, rows, n, lo, keys);
-    if ((rc = sort_pairs(keys, keys_sorted, rows, rows_sorted, N, bits_of((uint64_t)g_max - lo), s)) != PMI_OK) return rc;
+    if ((rc = sort_by_column(group, g_min, g_max, false, keys, keys_sorted, rows, rows_sorted, n, s)) != PMI_OK) return rc;
     PMI_LAUNCH((gather_xy_kernel<TX, TY>), n, s, x, y, rows_sorted, n, xs, ys);
     PMI_LAUNCH(hull_kernel, G, s, xs, ys, start, n, G, stack, area);
     PMI_HIP(hipStreamSynchronize(s));
-    return PMI_OK;
-}
-
-static int check_rows(const char *what, int64_t n, int64_t n_groups)
-{
-    if (n < 0 || n > INT32_MAX - 1 || n_groups < 0 || n_groups > n) {
-        set_error("%s: %lld rows, %lld labels (rows are indexed with int32)", what, (long long)n, (long long)n_groups);
-        return PMI_ERR_ARG;
-    }
     return PMI_OK;
 }
 
@@ -423,7 +353,7 @@ extern "C" {
 int pmi_centers_order_dev(const int64_t *d_group, int64_t n, int64_t g_min, int64_t g_max, int32_t *d_rows,
                           int32_t *d_start, int64_t *d_unique, int64_t *n_groups, void *stream)
 {
-    int rc = centers::check_rows("pmi_centers_order_dev", n, 0);
+    int rc = rows::check_rows("pmi_centers_order_dev", n, 0, "labels");
     if (rc) return rc;
     if (!n_groups || g_max < g_min || (n > 0 && (!d_group || !d_rows || !d_start || !d_unique))) {
         set_error("pmi_centers_order_dev: labels %lld .. %lld, or a NULL column", (long long)g_min, (long long)g_max);
@@ -436,7 +366,7 @@ int pmi_centers_order_dev(const int64_t *d_group, int64_t n, int64_t g_min, int6
 
 int pmi_centers_weights_dev(const void *d_lpx, const void *d_lpy, int type, int64_t n, void *d_w, void *stream)
 {
-    int rc = centers::check_rows("pmi_centers_weights_dev", n, 0);
+    int rc = rows::check_rows("pmi_centers_weights_dev", n, 0, "labels");
     if (rc) return rc;
     if (!centers::floating(type) || (n > 0 && (!d_lpx || !d_lpy || !d_w))) {
         set_error("pmi_centers_weights_dev: type %d, or a NULL column", type);
@@ -455,7 +385,7 @@ int pmi_centers_weights_dev(const void *d_lpx, const void *d_lpy, int type, int6
 int pmi_centers_stats_dev(const int32_t *d_rows, const int32_t *d_start, int64_t n, int64_t n_groups,
                           const pmi_centers_column *columns, int n_columns, void *stream)
 {
-    int rc = centers::check_rows("pmi_centers_stats_dev", n, n_groups);
+    int rc = rows::check_rows("pmi_centers_stats_dev", n, n_groups, "labels");
     if (rc) return rc;
     if (n_columns < 0 || n_columns > centers::MAX_COLS || (n_columns > 0 && !columns) ||
         (n > 0 && (!d_rows || !d_start))) {
@@ -490,7 +420,7 @@ int pmi_centers_hull_dev(const void *d_x, int x_type, const void *d_y, int y_typ
                          int64_t g_min, int64_t g_max, const int32_t *d_start, int64_t n, int64_t n_groups,
                          double *d_area, void *stream)
 {
-    int rc = centers::check_rows("pmi_centers_hull_dev", n, n_groups);
+    int rc = rows::check_rows("pmi_centers_hull_dev", n, n_groups, "labels");
     if (rc) return rc;
     if (!centers::floating(x_type) || !centers::floating(y_type) || g_max < g_min ||
         (n > 0 && (!d_x || !d_y || !d_group || !d_start)) || (n_groups > 0 && !d_area)) {

@@ -27,7 +27,7 @@
 //
 // Every loop is bounded by the row count; no float atomics; an inconsistent table gives an empty run.
 #include "knn_search.h"
-#include "rows_common.h"
+#include "rows_groups.h"
 #include "segment_stats.h"
 
 #pragma clang fp contract(off)
@@ -39,34 +39,7 @@ using namespace rows;
 
 constexpr int MAX_COLS = 32;
 
-__device__ __forceinline__ bool row_ok(int32_t i, int32_t n) { return (uint32_t)i < (uint32_t)n; }
-
-static int bits_of(uint64_t top)
-{
-    int bits = 1;
-    while (bits < 64 && (top >> bits)) bits++;
-    return bits;
-}
-
 // ---- order -----------------------------------------------------------------------------------------------------
-__global__ void cluster_key_kernel(const int64_t *__restrict__ cluster, int32_t n, uint64_t c_min,
-                                   uint64_t *__restrict__ keys, int32_t *__restrict__ rows)
-{
-    const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n) return;
-    keys[i] = (uint64_t)cluster[i] - c_min;
-    rows[i] = (int32_t)i;
-}
-
-__global__ void group_key_kernel(const int64_t *__restrict__ group, const int32_t *__restrict__ rows, int32_t n,
-                                 uint64_t g_min, uint64_t *__restrict__ keys)
-{
-    const int64_t p = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (p >= n) return;
-    const int32_t i = rows[p];
-    keys[p] = row_ok(i, n) ? (uint64_t)group[i] - g_min : 0;
-}
-
 // seg_flag[p]: a new (group, cluster) pair starts at sorted position p; grp_flag[p]: a new group does
 __global__ void flag_kernel(const uint64_t *__restrict__ group_keys, const int64_t *__restrict__ cluster,
                             const int32_t *__restrict__ rows, int32_t n, uint32_t *__restrict__ seg_flag,
@@ -95,18 +68,16 @@ __global__ void start_kernel(const uint64_t *__restrict__ group_keys, const int6
 {
     const int64_t p = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (p >= n) return;
-    const uint32_t s = seg_pos[p], g = grp_pos[p];
+    const uint32_t s = seg_pos[p];
+    const uint32_t S = close_runs(p, n, seg_flag[p], s, (int32_t)p, n, start);
+    // a group starts at a segment and the groups are closed by the number of segments
+    const uint32_t G = close_runs(p, n, grp_flag[p], grp_pos[p], (int32_t)s, (int32_t)(S <= (uint32_t)n ? S : 0), group_start);
     if (seg_flag[p] && s < (uint32_t)n) {
         const int32_t i = rows[p];
-        start[s] = (int32_t)p;
         seg_group[s] = (int64_t)(group_keys[p] + g_min);
         seg_cluster[s] = row_ok(i, n) ? cluster[i] : 0;
     }
-    if (grp_flag[p] && g < (uint32_t)n) group_start[g] = (int32_t)s;
     if (p == n - 1) {
-        const uint32_t S = s + seg_flag[p], G = g + grp_flag[p];
-        if (S <= (uint32_t)n) start[S] = n;
-        if (G <= (uint32_t)n) group_start[G] = (int32_t)(S <= (uint32_t)n ? S : 0);
         totals[0] = S;
         totals[1] = G;
     }
@@ -130,10 +101,8 @@ static int order(const int64_t *group, const int64_t *cluster, int32_t n, int64_
     // tables that the kernels below do not fill (they fill all of them on a consistent input) hold empty runs
     PMI_HIP(hipMemsetAsync(start, 0, (N + 1) * sizeof(int32_t), s));
     PMI_HIP(hipMemsetAsync(group_start, 0, (N + 1) * sizeof(int32_t), s));
-    PMI_LAUNCH(cluster_key_kernel, n, s, cluster, n, (uint64_t)c_min, keys, rows);
-    if ((rc = sort_pairs(keys, keys_sorted, rows, rows_mid, N, bits_of((uint64_t)c_max - (uint64_t)c_min), s)) != PMI_OK) return rc;
-    PMI_LAUNCH(group_key_kernel, n, s, group, rows_mid, n, (uint64_t)g_min, keys);
-    if ((rc = sort_pairs(keys, keys_sorted, rows_mid, rows_out, N, bits_of((uint64_t)g_max - (uint64_t)g_min), s)) != PMI_OK) return rc;
+    if ((rc = sort_by_column(cluster, c_min, c_max, true, keys, keys_sorted, rows, rows_mid, n, s)) != PMI_OK) return rc;
+    if ((rc = sort_by_column(group, g_min, g_max, false, keys, keys_sorted, rows_mid, rows_out, n, s)) != PMI_OK) return rc;
     PMI_LAUNCH(flag_kernel, n, s, keys_sorted, cluster, rows_out, n, seg_flag, grp_flag);
     if ((rc = exclusive_scan_u32(seg_flag, seg_pos, N, s)) != PMI_OK) return rc;
     if ((rc = exclusive_scan_u32(grp_flag, grp_pos, N, s)) != PMI_OK) return rc;
@@ -152,24 +121,6 @@ static int order(const int64_t *group, const int64_t *cluster, int32_t n, int64_
 }
 
 // ---- statistics ------------------------------------------------------------------------------------------------
-// vs[p] = the value of sorted position p in the summing type A
-template <typename T, typename A>
-__global__ void gather_kernel(const T *__restrict__ data, const int32_t *__restrict__ rows, int32_t n, A *__restrict__ vs)
-{
-    const int64_t p = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (p >= n) return;
-    const int32_t i = rows[p];
-    vs[p] = row_ok(i, n) ? (A)data[i] : (A)0;
-}
-
-// [a, b) of segment s; an inconsistent start table gives an empty run, never a read out of bounds
-__device__ __forceinline__ void run_of(const int32_t *__restrict__ start, int32_t s, int32_t n, int32_t *a, int32_t *b)
-{
-    *a = start[s];
-    *b = start[s + 1];
-    if (*a < 0 || *b > n || *a > *b) *a = *b = 0;
-}
-
 template <typename A>
 __global__ void moments_kernel(const A *__restrict__ vs, const int32_t *__restrict__ start, int32_t n, int32_t n_segments,
                                double *__restrict__ mean, double *__restrict__ sd)
@@ -196,10 +147,11 @@ __global__ void average_kernel(const T *__restrict__ xs, const T *__restrict__ w
     if (weight_sum) weight_sum[g] = scl;
 }
 
-template <typename T, typename A>
+template <typename T>
 static int moments_typed(const pmi_combine_column &c, const int32_t *rows, const int32_t *start, int32_t n, int32_t S,
                          void *buf, hipStream_t s)
 {
+    using A = typename Column<T>::sum_type;
     PMI_LAUNCH((gather_kernel<T, A>), n, s, (const T *)c.data, rows, n, (A *)buf);
     PMI_LAUNCH(moments_kernel<A>, S, s, (const A *)buf, start, n, S, c.mean, c.std);
     return PMI_OK;
@@ -219,16 +171,10 @@ static int column(const pmi_combine_column &c, const int32_t *rows, const int32_
                   void *wbuf, hipStream_t s)
 {
     int rc = PMI_OK;
-    if (c.mean || c.std) {
-        switch (c.type) {
-        case PMI_CENTERS_F32: rc = moments_typed<float, float>(c, rows, start, n, S, buf, s); break;
-        case PMI_CENTERS_F64: rc = moments_typed<double, double>(c, rows, start, n, S, buf, s); break;
-        case PMI_CENTERS_U32: rc = moments_typed<uint32_t, double>(c, rows, start, n, S, buf, s); break;
-        case PMI_CENTERS_I32: rc = moments_typed<int32_t, double>(c, rows, start, n, S, buf, s); break;
-        case PMI_CENTERS_U64: rc = moments_typed<uint64_t, double>(c, rows, start, n, S, buf, s); break;
-        default: rc = moments_typed<int64_t, double>(c, rows, start, n, S, buf, s); break;
-        }
-    }
+    if (c.mean || c.std)
+        rc = with_column_type(c.type, [&](auto col) {
+            return moments_typed<typename decltype(col)::type>(c, rows, start, n, S, buf, s);
+        });
     if (rc == PMI_OK && (c.average || c.weight_sum))
         rc = c.type == PMI_CENTERS_F32 ? average_typed<float>(c, rows, start, n, S, buf, wbuf, s)
                                        : average_typed<double>(c, rows, start, n, S, buf, wbuf, s);
@@ -346,7 +292,8 @@ static int mindist(const double *x, const int32_t *rows, const int32_t *start, c
     return PMI_OK;
 }
 
-static int check_rows(const char *what, int64_t n, int64_t n_segments, int64_t n_groups)
+// rows in segments in groups: one level more than rows::check_rows, and its own message
+static int check_table(const char *what, int64_t n, int64_t n_segments, int64_t n_groups)
 {
     if (n < 0 || n > INT32_MAX - 1 || n_segments < 0 || n_segments > n || n_groups < 0 || n_groups > n_segments) {
         set_error("%s: %lld rows, %lld segments, %lld groups (rows are indexed with int32)", what, (long long)n,
@@ -370,7 +317,7 @@ int pmi_combine_order_dev(const int64_t *d_group, const int64_t *d_cluster, int6
                           int64_t *d_seg_cluster, int32_t *d_group_start, int64_t *n_segments, int64_t *n_groups,
                           void *stream)
 {
-    int rc = combine::check_rows("pmi_combine_order_dev", n, 0, 0);
+    int rc = combine::check_table("pmi_combine_order_dev", n, 0, 0);
     if (rc) return rc;
     if (!n_segments || !n_groups || g_max < g_min || c_max < c_min ||
         (n > 0 && (!d_group || !d_cluster || !d_rows || !d_start || !d_seg_group || !d_seg_cluster || !d_group_start))) {
@@ -387,7 +334,7 @@ int pmi_combine_order_dev(const int64_t *d_group, const int64_t *d_cluster, int6
 int pmi_combine_stats_dev(const int32_t *d_rows, const int32_t *d_start, int64_t n, int64_t n_segments,
                           const pmi_combine_column *columns, int n_columns, void *stream)
 {
-    int rc = combine::check_rows("pmi_combine_stats_dev", n, n_segments, 0);
+    int rc = combine::check_table("pmi_combine_stats_dev", n, n_segments, 0);
     if (rc) return rc;
     if (n_columns < 0 || n_columns > combine::MAX_COLS || (n_columns > 0 && !columns) ||
         (n > 0 && (!d_rows || !d_start))) {
@@ -419,7 +366,7 @@ int pmi_combine_mindist_dev(const double *d_points, int dims, const int32_t *d_r
                             const int32_t *d_group_start, int64_t n, int64_t n_segments, int64_t n_groups,
                             double *d_min_dist, double *d_min_dist_xy, void *stream)
 {
-    int rc = combine::check_rows("pmi_combine_mindist_dev", n, n_segments, n_groups);
+    int rc = combine::check_table("pmi_combine_mindist_dev", n, n_segments, n_groups);
     if (rc) return rc;
     if ((dims != 2 && dims != 3) || (n > 0 && (!d_points || !d_rows || !d_start || !d_group_start || !d_min_dist)) ||
         (n > 0 && dims == 3 && !d_min_dist_xy)) {

@@ -20,7 +20,7 @@
 // are segment_stats.h's, which combine.hip shares.
 //
 // Every loop is bounded by the row count; no float atomics; an inconsistent table gives an empty run.
-#include "rows_common.h"
+#include "rows_groups.h"
 #include "segment_stats.h"
 
 #pragma clang fp contract(off)
@@ -32,34 +32,7 @@ using namespace rows;
 
 constexpr int MAX_COLS = 64;
 
-__device__ __forceinline__ bool row_ok(int32_t i, int32_t n) { return (uint32_t)i < (uint32_t)n; }
-
-static int bits_of(uint64_t top)
-{
-    int bits = 1;
-    while (bits < 64 && (top >> bits)) bits++;
-    return bits;
-}
-
 // ---- dark times: order -----------------------------------------------------------------------------------------
-__global__ void last_key_kernel(const int64_t *__restrict__ last, int32_t n, uint64_t l_min, uint64_t *__restrict__ keys,
-                                int32_t *__restrict__ rows)
-{
-    const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n) return;
-    keys[i] = (uint64_t)last[i] - l_min;
-    rows[i] = (int32_t)i;
-}
-
-__global__ void group_key_kernel(const int64_t *__restrict__ group, const int32_t *__restrict__ rows, int32_t n,
-                                 uint64_t g_min, uint64_t *__restrict__ keys)
-{
-    const int64_t p = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (p >= n) return;
-    const int32_t i = rows[p];
-    keys[p] = row_ok(i, n) ? (uint64_t)group[i] - g_min : 0;
-}
-
 __global__ void flag_kernel(const uint64_t *__restrict__ keys, const int64_t *__restrict__ last,
                             const int32_t *__restrict__ rows, int32_t n, uint32_t *__restrict__ flag,
                             int64_t *__restrict__ last_sorted)
@@ -77,10 +50,8 @@ __global__ void start_kernel(const uint32_t *__restrict__ flag, const uint32_t *
 {
     const int64_t p = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (p >= n) return;
-    const uint32_t g = pos[p] + flag[p];          // runs up to and including this position; >= 1
-    run[p] = (int32_t)g - 1;
-    if (flag[p] && g - 1 < (uint32_t)n) start[g - 1] = (int32_t)p;
-    if (p == n - 1 && g <= (uint32_t)n) start[g] = n;
+    // the runs up to and including this position, >= 1: a position that is not flagged lies in the run before pos[p]
+    run[p] = (int32_t)close_runs(p, n, flag[p], pos[p], (int32_t)p, n, start) - 1;
 }
 
 static int dark_order(const int64_t *last, const int64_t *group, int32_t n, int64_t l_min, int64_t l_max, int64_t g_min,
@@ -98,10 +69,8 @@ static int dark_order(const int64_t *last, const int64_t *group, int32_t n, int6
     if (rc != PMI_OK) return rc;
     // a start table that the kernels below do not fill (they fill all of it on a consistent input) holds empty runs
     PMI_HIP(hipMemsetAsync(start, 0, (N + 1) * sizeof(int32_t), s));
-    PMI_LAUNCH(last_key_kernel, n, s, last, n, (uint64_t)l_min, keys, rows);
-    if ((rc = sort_pairs(keys, keys_sorted, rows, rows_mid, N, bits_of((uint64_t)l_max - (uint64_t)l_min), s)) != PMI_OK) return rc;
-    PMI_LAUNCH(group_key_kernel, n, s, group, rows_mid, n, (uint64_t)g_min, keys);
-    if ((rc = sort_pairs(keys, keys_sorted, rows_mid, rows_out, N, bits_of((uint64_t)g_max - (uint64_t)g_min), s)) != PMI_OK) return rc;
+    if ((rc = sort_by_column(last, l_min, l_max, true, keys, keys_sorted, rows, rows_mid, n, s)) != PMI_OK) return rc;
+    if ((rc = sort_by_column(group, g_min, g_max, false, keys, keys_sorted, rows_mid, rows_out, n, s)) != PMI_OK) return rc;
     PMI_LAUNCH(flag_kernel, n, s, keys_sorted, last, rows_out, n, flag, last_sorted);
     if ((rc = exclusive_scan_u32(flag, pos, N, s)) != PMI_OK) return rc;
     PMI_LAUNCH(start_kernel, n, s, flag, pos, n, start, run);
@@ -121,8 +90,9 @@ __global__ void dark_kernel(const int64_t *__restrict__ frame, const int32_t *__
     int64_t out = -1;
     const int32_t g = run[q];
     if (row_ok(g, n)) {
-        const int32_t a = start[g], b = start[g + 1];
-        if (a >= 0 && a <= q && q < b && b <= n) {
+        int32_t a, b;
+        run_of(start, g, n, &a, &b);
+        if (a <= q && q < b) {
             const int64_t f = frame[i];
             int32_t p = lower_bound(last_sorted, a, b, f) - 1;      // the last position of the run that ends before f
             if (p == (int32_t)q) --p;                               // the row itself is no candidate
@@ -136,32 +106,23 @@ __global__ void dark_kernel(const int64_t *__restrict__ frame, const int32_t *__
 }
 
 // ---- group properties ------------------------------------------------------------------------------------------
-// vs[p] = the value of sorted position p in the summing type A
-template <typename T, typename A>
-__global__ void gather_kernel(const T *__restrict__ data, const int32_t *__restrict__ rows, int32_t n, A *__restrict__ vs)
-{
-    const int64_t p = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (p >= n) return;
-    const int32_t i = rows[p];
-    vs[p] = row_ok(i, n) ? (A)data[i] : (A)0;
-}
-
 template <typename A>
 __global__ void stats_kernel(const A *__restrict__ vs, const int32_t *__restrict__ start, int32_t n, int32_t n_groups,
                              double *__restrict__ mean, double *__restrict__ sd)
 {
     const int64_t g = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (g >= n_groups) return;
-    int32_t a = start[g], b = start[g + 1];
-    if (a < 0 || b > n || a > b) a = b = 0;      // an inconsistent start table: an empty run
+    int32_t a, b;
+    run_of(start, (int32_t)g, n, &a, &b);
     if (mean) mean[g] = segstats::series_mean<A>(vs, a, b);
     if (sd) sd[g] = segstats::series_std<A>(vs, a, b);
 }
 
-template <typename T, typename A>
+template <typename T>
 static int column_typed(const pmi_kinetics_column &c, const int32_t *rows, const int32_t *start, int32_t n, int32_t G,
                         void *buf, hipStream_t s)
 {
+    using A = typename Column<T>::sum_type;
     PMI_LAUNCH((gather_kernel<T, A>), n, s, (const T *)c.data, rows, n, (A *)buf);
     PMI_LAUNCH(stats_kernel<A>, G, s, (const A *)buf, start, n, G, c.mean, c.std);
     return PMI_OK;
@@ -170,23 +131,9 @@ static int column_typed(const pmi_kinetics_column &c, const int32_t *rows, const
 static int column(const pmi_kinetics_column &c, const int32_t *rows, const int32_t *start, int32_t n, int32_t G, void *buf,
                   hipStream_t s)
 {
-    switch (c.type) {
-    case PMI_CENTERS_F32: return column_typed<float, float>(c, rows, start, n, G, buf, s);
-    case PMI_CENTERS_F64: return column_typed<double, double>(c, rows, start, n, G, buf, s);
-    case PMI_CENTERS_U32: return column_typed<uint32_t, double>(c, rows, start, n, G, buf, s);
-    case PMI_CENTERS_I32: return column_typed<int32_t, double>(c, rows, start, n, G, buf, s);
-    case PMI_CENTERS_U64: return column_typed<uint64_t, double>(c, rows, start, n, G, buf, s);
-    default: return column_typed<int64_t, double>(c, rows, start, n, G, buf, s);
-    }
-}
-
-static int check_rows(const char *what, int64_t n, int64_t n_groups)
-{
-    if (n < 0 || n > INT32_MAX - 1 || n_groups < 0 || n_groups > n) {
-        set_error("%s: %lld rows, %lld groups (rows are indexed with int32)", what, (long long)n, (long long)n_groups);
-        return PMI_ERR_ARG;
-    }
-    return PMI_OK;
+    return with_column_type(c.type, [&](auto col) {
+        return column_typed<typename decltype(col)::type>(c, rows, start, n, G, buf, s);
+    });
 }
 
 }  // namespace kinetics
@@ -200,7 +147,7 @@ int pmi_kinetics_dark_order_dev(const int64_t *d_last, const int64_t *d_group, i
                                 int64_t g_min, int64_t g_max, int32_t *d_rows, int64_t *d_last_sorted, int32_t *d_run,
                                 int32_t *d_start, void *stream)
 {
-    int rc = kinetics::check_rows("pmi_kinetics_dark_order_dev", n, 0);
+    int rc = rows::check_rows("pmi_kinetics_dark_order_dev", n, 0, "groups");
     if (rc) return rc;
     if (l_max < l_min || g_max < g_min ||
         (n > 0 && (!d_last || !d_group || !d_rows || !d_last_sorted || !d_run || !d_start))) {
@@ -217,7 +164,7 @@ int pmi_kinetics_dark_search_dev(const int64_t *d_frame, const int32_t *d_rows, 
                                  const int32_t *d_run, const int32_t *d_start, int64_t n, int64_t max_frame,
                                  int64_t *d_dark, void *stream)
 {
-    int rc = kinetics::check_rows("pmi_kinetics_dark_search_dev", n, 0);
+    int rc = rows::check_rows("pmi_kinetics_dark_search_dev", n, 0, "groups");
     if (rc) return rc;
     if (n > 0 && (!d_frame || !d_rows || !d_last_sorted || !d_run || !d_start || !d_dark)) {
         set_error("pmi_kinetics_dark_search_dev: a NULL column");
@@ -235,7 +182,7 @@ int pmi_kinetics_dark_search_dev(const int64_t *d_frame, const int32_t *d_rows, 
 int pmi_kinetics_stats_dev(const int32_t *d_rows, const int32_t *d_start, int64_t n, int64_t n_groups,
                            const pmi_kinetics_column *columns, int n_columns, void *stream)
 {
-    int rc = kinetics::check_rows("pmi_kinetics_stats_dev", n, n_groups);
+    int rc = rows::check_rows("pmi_kinetics_stats_dev", n, n_groups, "groups");
     if (rc) return rc;
     if (n_columns < 0 || n_columns > kinetics::MAX_COLS || (n_columns > 0 && !columns) ||
         (n > 0 && (!d_rows || !d_start))) {

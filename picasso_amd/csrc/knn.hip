@@ -99,13 +99,6 @@ static int check_grid(const char *what, const Grid &g, int64_t m)
     return PMI_OK;
 }
 
-static int bits_of(uint32_t top)
-{
-    int bits = 1;
-    while (bits < 32 && (top >> bits)) bits++;
-    return bits;
-}
-
 template <int D>
 static int order(const double *x2, int32_t m, const Grid &g, double *sorted, int32_t *start, hipStream_t s)
 {
@@ -119,7 +112,7 @@ static int order(const double *x2, int32_t m, const Grid &g, double *sorted, int
     });
     if (rc != PMI_OK) return rc;
     PMI_LAUNCH(key_kernel<D>, m, s, g, x2, m, keys, rows);
-    if ((rc = sort_pairs(keys, keys_out, rows, rows_out, M, bits_of((uint32_t)(cells - 1)), s)) != PMI_OK) return rc;
+    if ((rc = sort_pairs(keys, keys_out, rows, rows_out, M, bits_of((uint64_t)(cells - 1)), s)) != PMI_OK) return rc;
     PMI_LAUNCH(gather_kernel<D>, m, s, x2, rows_out, m, sorted);
     PMI_LAUNCH(start_kernel, cells + 1, s, keys_out, m, cells, start);
     PMI_HIP(hipStreamSynchronize(s));

@@ -323,24 +323,6 @@ __global__ void combine_kernel(const uint32_t *__restrict__ sorted_group, const 
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------
-static int check_rows(const char *what, int64_t n)
-{
-    if (n < 0 || n > INT32_MAX - 1) {
-        set_error("%s: %lld rows (this kernel indexes rows with int32)", what, (long long)n);
-        return PMI_ERR_ARG;
-    }
-    return PMI_OK;
-}
-
-static int check_xy(const char *what, int x_type, int y_type)
-{
-    if ((x_type != PMI_LINK_F32 && x_type != PMI_LINK_F64) || (y_type != PMI_LINK_F32 && y_type != PMI_LINK_F64)) {
-        set_error("%s: x / y must be float32 or float64 (codes %d, %d)", what, x_type, y_type);
-        return PMI_ERR_ARG;
-    }
-    return PMI_OK;
-}
-
 static int frame_index(const int64_t *d_frame, int32_t n, int64_t k, int32_t *lo, int32_t *hi, hipStream_t s)
 {
     if (n == 0) return PMI_OK;
@@ -352,9 +334,7 @@ static int frame_index(const int64_t *d_frame, int32_t n, int64_t k, int32_t *lo
 static int sort_rows(uint32_t *keys, uint32_t *keys_out, int32_t *rows, int32_t *rows_out, int32_t n, int64_t key_end,
                      hipStream_t s)
 {
-    int bits = 1;
-    while (bits < 32 && (int64_t(1) << bits) < key_end) bits++;
-    return sort_pairs(keys, keys_out, rows, rows_out, (size_t)n, bits, s);
+    return sort_pairs(keys, keys_out, rows, rows_out, (size_t)n, bits_of((uint64_t)(key_end - 1)), s);
 }
 
 template <typename TX, typename TY>
@@ -433,7 +413,7 @@ extern "C" {
 
 int pmi_link_frame_index_dev(const int64_t *d_frame, int64_t n, int64_t k, int32_t *d_lo, int32_t *d_hi, void *stream)
 {
-    int rc = link::check_rows("pmi_link_frame_index_dev", n);
+    int rc = rows::check_rows("pmi_link_frame_index_dev", n);
     if (rc) return rc;
     if (n > 0 && (!d_frame || !d_lo || !d_hi)) {
         set_error("pmi_link_frame_index_dev: NULL column");
@@ -446,8 +426,8 @@ int pmi_link_groups_dev(const int64_t *d_frame, const void *d_x, int x_type, con
                         const int64_t *d_group, int64_t n, double r2, int64_t k, int32_t *d_link_group,
                         int64_t *n_groups, void *stream)
 {
-    int rc = link::check_rows("pmi_link_groups_dev", n);
-    if (rc || (rc = link::check_xy("pmi_link_groups_dev", x_type, y_type))) return rc;
+    int rc = rows::check_rows("pmi_link_groups_dev", n);
+    if (rc || (rc = rows::check_xy("pmi_link_groups_dev", x_type, y_type))) return rc;
     if (!n_groups || (n > 0 && (!d_frame || !d_x || !d_y || !d_group || !d_link_group))) {
         set_error("pmi_link_groups_dev: NULL column");
         return PMI_ERR_ARG;
@@ -462,7 +442,7 @@ int pmi_link_combine_dev(const int32_t *d_link_group, int64_t n, int64_t n_group
                          const pmi_link_column *columns, int n_columns, uint32_t *d_count, int64_t *d_first,
                          int64_t *d_last, int32_t *d_last_row, void *stream)
 {
-    int rc = link::check_rows("pmi_link_combine_dev", n);
+    int rc = rows::check_rows("pmi_link_combine_dev", n);
     if (rc) return rc;
     if (n_groups < 0 || n_groups > INT32_MAX - 1 || n_columns < 0 || n_columns > link::MAX_COLS ||
         (n_columns > 0 && !columns) || (n > 0 && !d_link_group) || (n_groups > 0 && (!d_count || !d_last_row))) {
@@ -510,8 +490,8 @@ int pmi_nena_hist_dev(const int64_t *d_frame, const void *d_x, int x_type, const
                       const int64_t *d_group, int64_t n, double d_max, double bin_size, int n_bins, uint64_t *d_hist,
                       void *stream)
 {
-    int rc = link::check_rows("pmi_nena_hist_dev", n);
-    if (rc || (rc = link::check_xy("pmi_nena_hist_dev", x_type, y_type))) return rc;
+    int rc = rows::check_rows("pmi_nena_hist_dev", n);
+    if (rc || (rc = rows::check_xy("pmi_nena_hist_dev", x_type, y_type))) return rc;
     if (n_bins < 1 || n_bins > link::MAX_BINS || !(bin_size > 0.0) || !d_hist ||
         (n > 0 && (!d_frame || !d_x || !d_y || !d_group))) {
         set_error("pmi_nena_hist_dev: %d bins of %g (at most %d), or a NULL column", n_bins, bin_size, link::MAX_BINS);

@@ -218,35 +218,6 @@ static int check_table(const char *what, int64_t n, int64_t p, int64_t K, int64_
     return PMI_OK;
 }
 
-static int check_xy(const char *what, int x_type, int y_type)
-{
-    if ((x_type != PMI_LINK_F32 && x_type != PMI_LINK_F64) || (y_type != PMI_LINK_F32 && y_type != PMI_LINK_F64)) {
-        set_error("%s: x / y must be float32 or float64 (codes %d, %d)", what, x_type, y_type);
-        return PMI_ERR_ARG;
-    }
-    return PMI_OK;
-}
-
-static int bits_of(uint32_t top)
-{
-    int bits = 1;
-    while (bits < 32 && (top >> bits)) bits++;
-    return bits;
-}
-
-// stable radix sort of (key, row) on the key bits [begin, end)
-static int sort_bits(uint64_t *keys, uint64_t *keys_out, int32_t *vals, int32_t *vals_out, size_t n, unsigned begin,
-                     unsigned end, hipStream_t stream)
-{
-    size_t bytes = 0;
-    PMI_HIP(rocprim::radix_sort_pairs(nullptr, bytes, keys, keys_out, vals, vals_out, n, begin, end, stream));
-    void *tmp = nullptr;
-    const int rc = scratch(SCR_STAGE_B, bytes + 64, &tmp);
-    if (rc != PMI_OK) return rc;
-    PMI_HIP(rocprim::radix_sort_pairs(tmp, bytes, keys, keys_out, vals, vals_out, n, begin, end, stream));
-    return PMI_OK;
-}
-
 static int order(const uint32_t *x_index, const uint32_t *y_index, int32_t n, int64_t K, int64_t L, int32_t *rows_out,
                  uint64_t *keys_out, int64_t *p, hipStream_t s)
 {
@@ -266,9 +237,9 @@ static int order(const uint32_t *x_index, const uint32_t *y_index, int32_t n, in
     PMI_HIP(hipMemcpyAsync(h_top, top, 8, hipMemcpyDeviceToHost, s));
     PMI_HIP(hipMemcpyAsync(stall, &n, 4, hipMemcpyHostToDevice, s));
     PMI_HIP(hipStreamSynchronize(s));
-    if ((rc = sort_bits(keys, keys_mid, rows, rows_mid, N, 0, (unsigned)bits_of(h_top[0]), s)) != PMI_OK) return rc;
-    if ((rc = sort_bits(keys_mid, keys_out, rows_mid, rows_out, N, 32, 32u + (unsigned)bits_of(h_top[1]), s)) != PMI_OK)
-        return rc;
+    // the x bits, then the y bits
+    if ((rc = sort_pairs(keys, keys_mid, rows, rows_mid, N, bits_of(h_top[0]), s)) != PMI_OK) return rc;
+    if ((rc = sort_pairs(keys_mid, keys_out, rows_mid, rows_out, N, bits_of(h_top[1]), s, 32)) != PMI_OK) return rc;
     PMI_LAUNCH(stall_kernel, n, s, keys_out, n, K, L, stall);
     int32_t h_stall = n;
     PMI_HIP(hipMemcpyAsync(&h_stall, stall, 4, hipMemcpyDeviceToHost, s));
@@ -358,7 +329,7 @@ int pmi_pairs_density_dev(const void *d_x, int x_type, const void *d_y, int y_ty
                           uint32_t *d_density, void *stream)
 {
     int rc = pairs::check_table("pmi_pairs_density_dev", n, p, K, L);
-    if (rc || (rc = pairs::check_xy("pmi_pairs_density_dev", x_type, y_type))) return rc;
+    if (rc || (rc = rows::check_xy("pmi_pairs_density_dev", x_type, y_type))) return rc;
     if (n > 0 && (!d_x || !d_y || !d_rows || !d_keys || !d_density)) {
         set_error("pmi_pairs_density_dev: NULL column");
         return PMI_ERR_ARG;
@@ -373,7 +344,7 @@ int pmi_pairs_distance_hist_dev(const void *d_x, int x_type, const void *d_y, in
                                 double r2, double bin_size, int64_t n_bins, uint64_t *d_hist, void *stream)
 {
     int rc = pairs::check_table("pmi_pairs_distance_hist_dev", n, p, K, L);
-    if (rc || (rc = pairs::check_xy("pmi_pairs_distance_hist_dev", x_type, y_type))) return rc;
+    if (rc || (rc = rows::check_xy("pmi_pairs_distance_hist_dev", x_type, y_type))) return rc;
     if (n_bins < 0 || n_bins > INT32_MAX - 1 || !(bin_size > 0.0) || (n_bins > 0 && !d_hist) ||
         (n > 0 && (!d_x || !d_y || !d_rows || !d_keys))) {
         set_error("pmi_pairs_distance_hist_dev: %lld bins of %g, or a NULL column", (long long)n_bins, bin_size);

@@ -1,6 +1,7 @@
-// rows_common.h — what the kernels over a resident localization table share (aim.hip, link.hip, cluster.hip): launch
-// shape, bisection, union-find, the scratch arena and the rocPRIM sorts and scan.  It pulls in rocPRIM: only those
-// three sources include it, the fit kernels do not pay for it.
+// rows_common.h — what the kernels over a resident localization table share: launch shape, bisection, union-find, the
+// scratch arena, the rocPRIM sorts and scan, and the argument checks of a row table.  Every post-processing source
+// includes it (aim, link, cluster, pairs, knn, frc directly; centers, kinetics, combine, areas and average through
+// rows_groups.h, the layer for tables ordered by a label column).  It pulls in rocPRIM: the fit kernels do not pay for it.
 #pragma once
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -99,17 +100,25 @@ static int carve(int slot, Layout &&layout, size_t *used = nullptr)
     return PMI_OK;
 }
 
+// the bits a radix sort needs for keys 0 .. top: at least one
+static int bits_of(uint64_t top)
+{
+    int bits = 1;
+    while (bits < 64 && (top >> bits)) bits++;
+    return bits;
+}
+
 // The rocPRIM calls; each takes its temporary from SCR_STAGE_B, which no arena of these modules is carved from.
-// Stable radix sorts on the low `bits` of the keys.
+// Stable radix sorts on the key bits [begin, begin + bits).
 template <typename K, typename V>
-static int sort_pairs(K *keys, K *keys_out, V *vals, V *vals_out, size_t n, int bits, hipStream_t stream)
+static int sort_pairs(K *keys, K *keys_out, V *vals, V *vals_out, size_t n, int bits, hipStream_t stream, int begin = 0)
 {
     size_t bytes = 0;
-    PMI_HIP(rocprim::radix_sort_pairs(nullptr, bytes, keys, keys_out, vals, vals_out, n, 0, bits, stream));
+    PMI_HIP(rocprim::radix_sort_pairs(nullptr, bytes, keys, keys_out, vals, vals_out, n, begin, begin + bits, stream));
     void *tmp = nullptr;
     const int rc = scratch(SCR_STAGE_B, bytes + 64, &tmp);
     if (rc != PMI_OK) return rc;
-    PMI_HIP(rocprim::radix_sort_pairs(tmp, bytes, keys, keys_out, vals, vals_out, n, 0, bits, stream));
+    PMI_HIP(rocprim::radix_sort_pairs(tmp, bytes, keys, keys_out, vals, vals_out, n, begin, begin + bits, stream));
     return PMI_OK;
 }
 
@@ -136,6 +145,29 @@ static int exclusive_scan_u32(F *flag, uint32_t *out, size_t n, hipStream_t stre
     const int rc = scratch(SCR_STAGE_B, bytes + 64, &tmp);
     if (rc != PMI_OK) return rc;
     PMI_HIP(rocprim::exclusive_scan(tmp, bytes, flag, out, 0u, n, rocprim::plus<uint32_t>(), stream));
+    return PMI_OK;
+}
+
+// n rows, indexed with int32, in n_groups runs that `unit` names in the message (no unit: a call without runs)
+static int check_rows(const char *what, int64_t n, int64_t n_groups = 0, const char *unit = nullptr)
+{
+    if (n < 0 || n > INT32_MAX - 1 || n_groups < 0 || n_groups > n) {
+        if (unit)
+            set_error("%s: %lld rows, %lld %s (rows are indexed with int32)", what, (long long)n, (long long)n_groups, unit);
+        else
+            set_error("%s: %lld rows (this kernel indexes rows with int32)", what, (long long)n);
+        return PMI_ERR_ARG;
+    }
+    return PMI_OK;
+}
+
+// x / y type codes of pmi_link_type
+static int check_xy(const char *what, int x_type, int y_type)
+{
+    if ((x_type != PMI_LINK_F32 && x_type != PMI_LINK_F64) || (y_type != PMI_LINK_F32 && y_type != PMI_LINK_F64)) {
+        set_error("%s: x / y must be float32 or float64 (codes %d, %d)", what, x_type, y_type);
+        return PMI_ERR_ARG;
+    }
     return PMI_OK;
 }
 
