@@ -68,6 +68,10 @@
  *                      get_NN_dist (scipy.spatial.KDTree(X2).query(X1, k))
  *   pmi_frc_*, pmi_radial_sum  picasso/postprocess.py:1398-1502 _frc (from the two rendered histograms to the curve),
  *                      picasso/masking.py:649-671 threshold_tukey, picasso/imageprocess.py:283-321 radial_sum
+ *   pmi_picks_*        picasso/postprocess.py:207-372 _picked_circular_locs, _picked_rectangular_locs,
+ *                      _picked_polygonal_locs, _picked_square_locs (:375-473 picked_locs), :849-928
+ *                      _get_block_locs_at_numba, _locs_at_numba, picasso/lib.py:1884-2004 check_if_in_polygon,
+ *                      check_if_in_rectangle
  */
 #ifndef PICASSO_HIP_H
 #define PICASSO_HIP_H
@@ -887,6 +891,47 @@ int pmi_frc_curve(const float *im1, const float *im2, int64_t m, const double *w
 int pmi_frc_curve_dev(const float *d_im1, const float *d_im2, int64_t m, const double *d_w, double *d_sums, double *d_curve,
                       float *d_masked1, float *d_masked2, float *ms4, void *stream);
 int pmi_radial_sum(const void *image, int dtype, int64_t n, void *out);
+
+/* ---- picked localizations (picasso/postprocess.py:207-473, :849-928, picasso/lib.py:1884-2004, csrc/picks.hip) ------- *
+ * The member rows of every pick of one call, as a CSR pair: d_offsets[n_picks + 1] (int64) and d_members (int32 rows in
+ * the caller's row order).  Each of the two pick calls is made twice: with d_members == NULL it counts, fills d_offsets
+ * and *total (the one device-to-host copy, which sizes d_members); with d_members it reads d_offsets and writes at most
+ * `capacity` rows.  One workgroup per pick, all picks in one launch.  d_x / d_y are the table's columns, float32 or
+ * float64 (PMI_LINK_F32 / PMI_LINK_F64, each on its own); d_rows / d_keys / p are what pmi_pairs_order_dev returned.
+ * Every call runs on `stream` and synchronises it before it returns.  Divisions follow IEEE.
+ *
+ * pmi_picks_circle_dev   over the sanity-filtered table in the block order of get_index_blocks (K x L blocks of the pick
+ *                        radius).  Pick i lies at (d_pick_x[i], d_pick_y[i]) in block (d_block_y[i], d_block_x[i]) =
+ *                        int(y / r), int(x / r), computed by the host; it walks the blocks k = by - 1 .. by + 1,
+ *                        l = bx - 1 .. bx + 1 with 0 <= k < K, 0 <= l < L, k outside l, over the positions < p, and keeps
+ *                        the rows with dx ** 2 + dy ** 2 < r2 in that order (the reference's order before its sort by
+ *                        frame).  d_flags[i] bit 0 / bit 1 keep the x / y difference and its square in float32 when
+ *                        that column is float32 (an integer or float32 pick coordinate, as numba types it), bit 2
+ *                        compares a sum of two float32 squares with float32(r2); all else is float64.
+ * pmi_picks_cells_dev    the uint32 cell indices of every row on a grid of CX x CY cells of `cell` from (x0, y0); a row
+ *                        outside [x0, x1] x [y0, y1] (a NaN too) gets (x_index, y_index) = (0, CY), outside the grid.
+ *                        pmi_pairs_order_dev(.., K = CY, L = CX, ..) then gives the order pmi_picks_shape_dev walks.
+ * pmi_picks_shape_dev    shape 0 Square, 1 Rectangle, 2 Polygon over the whole table binned as above (the same grid
+ *                        arguments).  d_bounds[4 i ..] = x_min, x_max, y_min, y_max of pick i, strict; bit b of
+ *                        d_flags[i] says bound b is a weak (Python) scalar, compared in the column's own type, else the
+ *                        compare is float64.  Rectangle and Polygon then test the corners
+ *                        d_corner_x / d_corner_y [d_corner_offsets[i] .. d_corner_offsets[i + 1]) in float64, in the
+ *                        operation order of check_if_in_rectangle (4 corners) / check_if_in_polygon.  Members of a pick
+ *                        ascend by row (a segmented radix sort), as a boolean mask leaves them.                     */
+int pmi_picks_circle_dev(const void *d_x, int x_type, const void *d_y, int y_type, const int32_t *d_rows,
+                         const uint64_t *d_keys, int64_t n, int64_t p, int64_t K, int64_t L, const double *d_pick_x,
+                         const double *d_pick_y, const int64_t *d_block_x, const int64_t *d_block_y,
+                         const uint8_t *d_flags, int64_t n_picks, double r2, int64_t *d_offsets, int32_t *d_members,
+                         int64_t capacity, int64_t *total, void *stream);
+int pmi_picks_cells_dev(const void *d_x, int x_type, const void *d_y, int y_type, int64_t n, double x0, double y0,
+                        double x1, double y1, double cell, int64_t CX, int64_t CY, uint32_t *d_x_index,
+                        uint32_t *d_y_index, void *stream);
+int pmi_picks_shape_dev(const void *d_x, int x_type, const void *d_y, int y_type, const int32_t *d_rows,
+                        const uint64_t *d_keys, int64_t n, int64_t p, double x0, double y0, double x1, double y1,
+                        double cell, int64_t CX, int64_t CY, int shape, const double *d_bounds, const uint8_t *d_flags,
+                        const int32_t *d_corner_offsets, const double *d_corner_x, const double *d_corner_y,
+                        int64_t n_corners, int64_t n_picks, int64_t *d_offsets, int32_t *d_members, int64_t capacity,
+                        int64_t *total, void *stream);
 
 /* ---- timing hooks for bench.py (HIP events on the given stream) ------- */
 int pmi_event_create(void **event);

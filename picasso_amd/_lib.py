@@ -151,6 +151,11 @@ SYMBOLS = {
     "pmi_frc_curve": (_i32, [_p, _p, _i64, _p, _p, _p, _p, _p]),
     "pmi_frc_curve_dev": (_i32, [_p, _p, _i64, _p, _p, _p, _p, _p, _p, _p]),
     "pmi_radial_sum": (_i32, [_p, _i32, _i64, _p]),
+    "pmi_picks_circle_dev": (_i32, [_p, _i32, _p, _i32, _p, _p, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _p, _i64, _f64, _p,
+                                    _p, _i64, _p, _p]),
+    "pmi_picks_cells_dev": (_i32, [_p, _i32, _p, _i32, _i64, _f64, _f64, _f64, _f64, _f64, _i64, _i64, _p, _p, _p]),
+    "pmi_picks_shape_dev": (_i32, [_p, _i32, _p, _i32, _p, _p, _i64, _i64, _f64, _f64, _f64, _f64, _f64, _i64, _i64, _i32,
+                                   _p, _p, _p, _p, _p, _i64, _i64, _p, _p, _i64, _p, _p]),
     "pmi_event_create": (_i32, [_p]),
     "pmi_event_record": (_i32, [_p, _p]),
     "pmi_event_elapsed_ms": (_i32, [_p, _p, _p]),

@@ -927,7 +927,18 @@ class BlockTable:
         if x_index.dtype != np.uint32 or y_index.dtype != np.uint32 or x_index.shape != y_index.shape or x_index.ndim != 1:
             raise TypeError("x_index and y_index must be uint32 arrays of one length")
         self.n, self.K, self.L = int(len(x_index)), int(K), int(L)
-        d_xi, d_yi = _to_device(x_index), _to_device(y_index)
+        self._order(_to_device(x_index), _to_device(y_index))
+
+    @classmethod
+    def from_device(cls, d_x_index, d_y_index, K: int, L: int):
+        """The same over uint32 indices already on the device (int32 tensors holding their bits)."""
+        self = cls.__new__(cls)
+        self.n, self.K, self.L = int(len(d_x_index)), int(K), int(L)
+        self._order(d_x_index, d_y_index)
+        return self
+
+    def _order(self, d_xi, d_yi):
+        import torch
         self.device = d_xi.device
         self.stream = torch.cuda.current_stream(self.device).cuda_stream
         self.rows = torch.empty(max(self.n, 1), dtype=torch.int32, device=self.device)
@@ -971,6 +982,155 @@ class BlockTable:
                 float(r_max), float(r2), float(bin_size), int(n_bins), _dptr(hist), ctypes.c_void_p(self.stream)),
                 "pmi_pairs_distance_hist_dev")
             return hist[:int(n_bins)].cpu().numpy().view(np.uint64)
+
+
+# ---- picked localizations (csrc/picks.hip, picasso/postprocess.py:207-473, picasso/lib.py:1884-2004) ----
+PICK_SQUARE, PICK_RECTANGLE, PICK_POLYGON = 0, 1, 2
+PICK_MAX_CELLS = 1 << 14          # cells per axis of the grid the box shapes are binned on
+_PICK_FAR = 8e307                 # bounds are clipped here so that the grid's extent stays finite
+
+
+def _pick_column(a):
+    """A float32 / float64 column, host or device -> (device tensor, type code)."""
+    import torch
+    if isinstance(a, torch.Tensor):
+        if a.dtype not in (torch.float32, torch.float64) or a.dim() != 1 or not a.is_cuda:
+            raise TypeError("a device column must be a 1-D float32 or float64 tensor on the GPU")
+        return a.contiguous(), LINK_F32 if a.dtype == torch.float32 else LINK_F64
+    a = np.asarray(a)
+    return _to_device(a), link_type(a.dtype, True)
+
+
+def _picks_csr(call, n_picks: int, device):
+    """The two passes of a pick call: count (offsets and the total, the one copy to the host), then write."""
+    import torch
+    offsets = torch.zeros(n_picks + 1, dtype=torch.int64, device=device)
+    total = ctypes.c_int64(0)
+    _lib.check(call(_dptr(offsets), None, 0, ctypes.byref(total)), "pmi_picks (count)")
+    rows = torch.empty(max(int(total.value), 1), dtype=torch.int32, device=device)
+    if total.value:
+        _lib.check(call(_dptr(offsets), _dptr(rows), int(total.value), None), "pmi_picks (write)")
+    return offsets.cpu().numpy(), rows[:int(total.value)].cpu().numpy().astype(np.int64)
+
+
+def picks_circle(table: "BlockTable", x, y, pick_x, pick_y, block_x, block_y, flags, r2: float):
+    """Members of circular picks over a table in block order (``table`` built from uint32(x / r), uint32(y / r) of the
+    same rows) -> (int64 offsets[P + 1], int64 rows): per pick the rows with dx ** 2 + dy ** 2 < r2 of the blocks around
+    (block_y, block_x), in block order.  ``flags``: numba's typing of each pick, see pmi_picks_circle_dev."""
+    _lib.require_gpu()
+    d_x, tx = _pick_column(x)
+    d_y, ty = _pick_column(y)
+    if len(d_x) != table.n or len(d_y) != table.n:
+        raise ValueError("x and y must have one entry per row of the table")
+    P = len(pick_x)
+    if not (len(pick_y) == len(block_x) == len(block_y) == len(flags) == P):
+        raise ValueError("one coordinate pair, block pair and flag per pick")
+    if P == 0:
+        return np.zeros(1, np.int64), np.zeros(0, np.int64)
+    d_px, d_py = _to_device(pick_x, np.float64), _to_device(pick_y, np.float64)
+    # any block index beyond [-1, 2^32] names no block of the grid: clipped so that index + 1 cannot overflow
+    d_bx = _to_device(np.array([min(max(int(b), -2), 1 << 33) for b in block_x], np.int64))
+    d_by = _to_device(np.array([min(max(int(b), -2), 1 << 33) for b in block_y], np.int64))
+    d_f = _to_device(flags, np.uint8)
+    L = _lib.load()
+    with _lib.lock():
+        return _picks_csr(lambda off, rows, cap, total: L.pmi_picks_circle_dev(
+            _dptr(d_x), tx, _dptr(d_y), ty, _dptr(table.rows), _dptr(table.keys), table.n, table.p, table.K, table.L,
+            _dptr(d_px), _dptr(d_py), _dptr(d_bx), _dptr(d_by), _dptr(d_f), P, float(r2), off, rows, cap, total,
+            ctypes.c_void_p(table.stream)), P, table.device)
+
+
+def _pick_grid(bounds, flags, tx: int, ty: int):
+    """The grid the rows are binned on: it covers every pick's box as the rows are held against it (a weak bound of a
+    float32 column is rounded to float32), with cells of half the mean box side, at most PICK_MAX_CELLS per axis."""
+    eff = np.array(bounds, np.float64).reshape(-1, 4)
+    flags = np.asarray(flags, np.uint8)
+    for b in range(4):
+        if (tx if b < 2 else ty) == LINK_F32:
+            weak = (flags >> b) & 1 == 1
+            with np.errstate(over="ignore"):
+                eff[weak, b] = eff[weak, b].astype(np.float32).astype(np.float64)
+    eff = np.clip(eff, -_PICK_FAR, _PICK_FAR)           # NaN stays NaN
+    ok = (eff[:, 0] < eff[:, 1]) & (eff[:, 2] < eff[:, 3])
+    if not ok.any():
+        return 0.0, 0.0, 1.0, 1.0, 1.0, 1, 1
+    e = eff[ok]
+    x0, x1, y0, y1 = float(e[:, 0].min()), float(e[:, 1].max()), float(e[:, 2].min()), float(e[:, 3].max())
+    extent = max(x1 - x0, y1 - y0)
+    with np.errstate(over="ignore"):
+        cell = 0.5 * float(np.mean(np.r_[e[:, 1] - e[:, 0], e[:, 3] - e[:, 2]]))
+    cell = max(cell, extent / PICK_MAX_CELLS)
+    if not (np.isfinite(cell) and cell > 0):
+        cell = extent
+    CX = min(int((x1 - x0) / cell) + 1, PICK_MAX_CELLS + 1)
+    CY = min(int((y1 - y0) / cell) + 1, PICK_MAX_CELLS + 1)
+    return x0, y0, x1, y1, cell, CX, CY
+
+
+def _picks_shape(shape: int, x, y, bounds, flags, corner_offsets=None, corner_x=None, corner_y=None):
+    import torch
+    _lib.require_gpu()
+    d_x, tx = _pick_column(x)
+    d_y, ty = _pick_column(y)
+    n = len(d_x)
+    if len(d_y) != n:
+        raise ValueError("x and y must have one length")
+    bounds = np.ascontiguousarray(bounds, np.float64).reshape(-1, 4)
+    flags = np.ascontiguousarray(flags, np.uint8)
+    P = len(bounds)
+    if len(flags) != P:
+        raise ValueError("one flag byte per pick")
+    if P == 0:
+        return np.zeros(1, np.int64), np.zeros(0, np.int64)
+    n_corners = 0
+    d_co = d_cx = d_cy = None
+    if shape != PICK_SQUARE:
+        corner_offsets = np.ascontiguousarray(corner_offsets, np.int32)
+        corner_x, corner_y = np.ascontiguousarray(corner_x, np.float64), np.ascontiguousarray(corner_y, np.float64)
+        n_corners = len(corner_x)
+        if len(corner_offsets) != P + 1 or len(corner_y) != n_corners or corner_offsets[0] != 0 or \
+                corner_offsets[-1] != n_corners or (np.diff(corner_offsets) < 0).any():
+            raise ValueError("corner_offsets must be the P + 1 ascending offsets of the corner arrays")
+        if shape == PICK_RECTANGLE and (np.diff(corner_offsets) != 4).any():
+            raise ValueError("a rectangle has four corners")
+        d_co = _to_device(corner_offsets)
+        d_cx, d_cy = _to_device(np.r_[corner_x, 0.0]), _to_device(np.r_[corner_y, 0.0])
+    x0, y0, x1, y1, cell, CX, CY = _pick_grid(bounds, flags, tx, ty)
+    d_b, d_f = _to_device(bounds.reshape(-1)), _to_device(flags)
+    device = d_x.device
+    stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    d_xi = torch.empty(max(n, 1), dtype=torch.int32, device=device)
+    d_yi = torch.empty(max(n, 1), dtype=torch.int32, device=device)
+    L = _lib.load()
+    with _lib.lock():
+        _lib.check(L.pmi_picks_cells_dev(_dptr(d_x), tx, _dptr(d_y), ty, n, x0, y0, x1, y1, cell, CX, CY, _dptr(d_xi),
+                                         _dptr(d_yi), stream), "pmi_picks_cells_dev")
+    table = BlockTable.from_device(d_xi[:n], d_yi[:n], CY, CX)
+    with _lib.lock():
+        return _picks_csr(lambda off, rows, cap, total: L.pmi_picks_shape_dev(
+            _dptr(d_x), tx, _dptr(d_y), ty, _dptr(table.rows), _dptr(table.keys), n, table.p, x0, y0, x1, y1, cell, CX,
+            CY, shape, _dptr(d_b), _dptr(d_f), _dptr(d_co), _dptr(d_cx), _dptr(d_cy), n_corners, P, off, rows, cap,
+            total, stream), P, device)
+
+
+def picks_square(x, y, bounds, flags):
+    """Members of square picks over the whole table -> (int64 offsets[P + 1], int64 rows ascending per pick):
+    x_min < x < x_max and y_min < y < y_max with bounds[i] = (x_min, x_max, y_min, y_max); bit b of flags[i] marks bound
+    b as a weak Python scalar, compared in the column's dtype (else in float64)."""
+    return _picks_shape(PICK_SQUARE, x, y, bounds, flags)
+
+
+def picks_rectangle(x, y, bounds, flags, corner_x, corner_y):
+    """The same box, then check_if_in_rectangle against the (P, 4) corners, in float64."""
+    cx, cy = np.asarray(corner_x, np.float64).reshape(-1, 4), np.asarray(corner_y, np.float64).reshape(-1, 4)
+    return _picks_shape(PICK_RECTANGLE, x, y, bounds, flags, np.arange(len(cx) + 1, dtype=np.int32) * 4, cx.reshape(-1),
+                        cy.reshape(-1))
+
+
+def picks_polygon(x, y, bounds, flags, corner_offsets, corner_x, corner_y):
+    """The same box, then check_if_in_polygon against the corners
+    corner_x / corner_y [corner_offsets[i] : corner_offsets[i + 1]] of pick i, in float64."""
+    return _picks_shape(PICK_POLYGON, x, y, bounds, flags, corner_offsets, corner_x, corner_y)
 
 
 # ---- nearest-neighbour distances (csrc/knn.hip, picasso/postprocess.py:3704-3739, picasso/spinna.py:696-747) ----

@@ -838,3 +838,175 @@ def _frc(locs1: pd.DataFrame, locs2: pd.DataFrame, pixelsize: float, lp: float, 
     frequencies = np.arange(len(frc_curve)) / side / (pixelsize * binsize)
     resolution = _fire_resolution(frequencies, frc_curve_smooth)
     return frc_curve, frc_curve_smooth, frequencies, resolution, images
+
+
+# ---- picked localizations (postprocess.py:207-473, :739-799) --------------------------------------------------
+# Not rebound by localize.install(): the reference's picks family (pick_similar, the fiducial undrifts, the pick
+# kinetics) hands picked_locs a K x L ``index_blocks`` tuple, which this module does not build.
+PICK_NAMES = ("picked_locs", "_picked_circular_locs", "_picked_rectangular_locs", "_picked_polygonal_locs",
+              "_picked_square_locs", "remove_locs_in_picks")
+
+
+def _pick_done(i: int, callback, progress) -> None:
+    if callback == "console":
+        progress.update(1)
+    elif callback is not None:
+        callback(i + 1)
+
+
+def _pick_frames(locs: pd.DataFrame, offsets, rows, positions, add_group: bool, callback, progress, n_picks: int,
+                 finish=None) -> list[pd.DataFrame]:
+    """One frame per pick from the device's CSR pair: the member rows in the reference's order before its sort, then
+    the reference's own pandas calls (copy, ``group``, the quicksort by frame, which is not stable)."""
+    picked, at = [], dict(zip(positions, range(len(positions))))
+    for i in range(n_picks):
+        if i in at:
+            group_locs = locs.iloc[rows[offsets[at[i]]:offsets[at[i] + 1]]].copy()
+            if finish is not None:
+                finish(i, group_locs)
+            if add_group:
+                group_locs["group"] = i
+            group_locs.sort_values(by="frame", kind="quicksort", inplace=True)
+            picked.append(group_locs)
+        _pick_done(i, callback, progress)
+    return picked
+
+
+def _refuse_index_blocks(index_blocks) -> None:
+    if index_blocks is not None:
+        raise NotImplementedError("index_blocks: the K x L block table of get_index_blocks is not built here; "
+                                  "pass None and the blocks are ordered on the device")
+
+
+def _pick_bounds(boxes):
+    """(P, 4) float64 bounds and the weak-scalar bits of each: a Python int or float is compared in the column's dtype,
+    a NumPy scalar in the common type (NumPy 2 promotion, which the reference's pandas masks follow)."""
+    bounds = np.array([[float(v) for v in b] for b in boxes], np.float64).reshape(-1, 4)
+    flags = np.array([sum(1 << k for k, v in enumerate(b) if not isinstance(v, np.generic)) for b in boxes], np.uint8)
+    return bounds, flags
+
+
+def _keeps_float32(v) -> bool:
+    """numba: ``float32[:] (op) v`` stays float32 for an integer or float32 scalar, a float64 one widens it."""
+    return isinstance(v, (bool, int, np.integer, np.bool_, np.float32, np.float16))
+
+
+def _picked_circular_locs(locs: pd.DataFrame, info: list[dict], picks: list[tuple], pick_size: float,
+                          index_blocks: tuple | None, add_group: bool,
+                          callback: Callable[[int], None] | Literal["console"] | None, progress: tqdm | None) -> list[pd.DataFrame]:
+    """Circular picks (postprocess.py:207-253): the sanity-filtered table in block order, the nine blocks around each
+    pick, ``dx**2 + dy**2 < r**2`` as numba types it; all picks in one device call."""
+    _refuse_index_blocks(index_blocks)
+    locs = lib.ensure_sanity(locs, info)
+    x_index = np.uint32(locs["x"].to_numpy() / pick_size)
+    y_index = np.uint32(locs["y"].to_numpy() / pick_size)
+    n_blocks_y, n_blocks_x = _index_blocks_shape(info, pick_size)
+    table = backend.BlockTable(x_index, y_index, n_blocks_y, n_blocks_x)
+    block_x = [int(x / pick_size) for x, _ in picks]
+    block_y = [int(y / pick_size) for _, y in picks]
+    # the reference stacks x and y into one array: a float32 beside a float64 column is float64 before any arithmetic
+    both32 = locs["x"].dtype == np.float32 and locs["y"].dtype == np.float32
+    flags = [((1 if _keeps_float32(x) else 0) | (2 if _keeps_float32(y) else 0) | (4 if _keeps_float32(pick_size) else 0))
+             if both32 else 0 for x, y in picks]
+    if isinstance(pick_size, np.float32):
+        r2 = float(pick_size * pick_size)
+    elif isinstance(pick_size, (int, np.integer)):
+        r2 = float(int(pick_size) ** 2)
+    else:
+        r2 = float(np.float64(pick_size) * np.float64(pick_size))
+    offsets, rows = backend.picks_circle(table, locs["x"].to_numpy(), locs["y"].to_numpy(), [float(x) for x, _ in picks],
+                                         [float(y) for _, y in picks], block_x, block_y, flags, r2)
+    return _pick_frames(locs, offsets, rows, range(len(picks)), add_group, callback, progress, len(picks))
+
+
+def _picked_rectangular_locs(locs: pd.DataFrame, picks: list[tuple], pick_size: float, add_group: bool,
+                             callback: Callable[[int], None] | Literal["console"] | None, progress: tqdm | None) -> list[pd.DataFrame]:
+    """Rectangular picks (postprocess.py:256-298): the strict bounding box, the four-sided ray count, and the rotated
+    coordinates from the subset with the reference's own pandas expressions."""
+    corners = [lib.get_pick_rectangle_corners(xs, ys, xe, ye, pick_size) for (xs, ys), (xe, ye) in picks]
+    bounds, flags = _pick_bounds([(min(X), max(X), min(Y), max(Y)) for X, Y in corners])
+    offsets, rows = backend.picks_rectangle(locs["x"].to_numpy(), locs["y"].to_numpy(), bounds, flags,
+                                            [X for X, _ in corners], [Y for _, Y in corners])
+
+    def rotated(i, group_locs):
+        (xs, ys), (xe, ye) = picks[i]
+        angle = 0.5 * np.pi - np.arctan2((ye - ys), (xe - xs))
+        x_shifted = group_locs["x"] - xs
+        y_shifted = group_locs["y"] - ys
+        group_locs["x_pick_rot"] = x_shifted * np.cos(angle) - y_shifted * np.sin(angle)
+        group_locs["y_pick_rot"] = x_shifted * np.sin(angle) + y_shifted * np.cos(angle)
+
+    return _pick_frames(locs, offsets, rows, range(len(picks)), add_group, callback, progress, len(picks), rotated)
+
+
+def _picked_polygonal_locs(locs: pd.DataFrame, picks: list[tuple], add_group: bool,
+                           callback: Callable[[int], None] | Literal["console"] | None, progress: tqdm | None):
+    """Polygonal picks (postprocess.py:301-335): unclosed polygons are skipped (``group`` keeps the pick's position);
+    the strict bounding box, then the ray casting over the corners."""
+    kept, corners = [], []
+    for i, pick in enumerate(picks):
+        X, Y = lib.get_pick_polygon_corners(pick)
+        if X is not None:
+            kept.append(i)
+            corners.append((X, Y))
+    bounds, flags = _pick_bounds([(min(X), max(X), min(Y), max(Y)) for X, Y in corners])
+    corner_offsets = np.zeros(len(corners) + 1, np.int32)
+    corner_offsets[1:] = np.cumsum([len(X) for X, _ in corners])
+    corner_x = np.array([v for X, _ in corners for v in X], np.float64)
+    corner_y = np.array([v for _, Y in corners for v in Y], np.float64)
+    offsets, rows = backend.picks_polygon(locs["x"].to_numpy(), locs["y"].to_numpy(), bounds, flags, corner_offsets,
+                                          corner_x, corner_y)
+    return _pick_frames(locs, offsets, rows, kept, add_group, callback, progress, len(picks))
+
+
+def _picked_square_locs(locs: pd.DataFrame, picks: list[tuple], pick_size: float, add_group: bool,
+                        callback: Callable[[int], None] | Literal["console"] | None, progress: tqdm | None) -> list[pd.DataFrame]:
+    """Square picks (postprocess.py:338-372): the strict box of side ``pick_size`` around each pick."""
+    half_a = pick_size / 2
+    bounds, flags = _pick_bounds([(x - half_a, x + half_a, y - half_a, y + half_a) for x, y in picks])
+    offsets, rows = backend.picks_square(locs["x"].to_numpy(), locs["y"].to_numpy(), bounds, flags)
+    return _pick_frames(locs, offsets, rows, range(len(picks)), add_group, callback, progress, len(picks))
+
+
+PICK_SHAPES = ("Circle", "Rectangle", "Polygon", "Square")
+
+
+def picked_locs(locs: pd.DataFrame, info: list[dict], picks: list[tuple],
+                pick_shape: Literal["Circle", "Rectangle", "Polygon", "Square"], pick_size: float = None,
+                add_group: bool = True, index_blocks: tuple = None,
+                callback: Callable[[int], None] | Literal["console"] | None = None) -> list[pd.DataFrame]:
+    """The localizations within each pick (postprocess.py:375-473): a list of frames, one per pick, each a copy of the
+    member rows with their index labels, ``group`` = the pick's position when ``add_group``, sorted by frame.
+    ``pick_size`` is the radius of a circle, the width of a rectangle, the side of a square.  The members of all picks
+    are found in one device call; a non-None ``index_blocks`` is refused.  ``callback`` sees 1 .. len(picks), or is
+    ``"console"`` for a tqdm bar."""
+    assert pick_shape in PICK_SHAPES, f"Invalid pick shape: {pick_shape}. Choose one of {PICK_SHAPES}."
+    if len(picks) == 0:
+        return []
+    progress = None
+    if callback == "console":
+        from tqdm import tqdm
+        progress = tqdm(range(len(picks)), desc="Picking locs", unit="pick")
+    common = dict(locs=locs, picks=picks, add_group=add_group, callback=callback, progress=progress)
+    if pick_shape == "Circle":
+        return _picked_circular_locs(info=info, pick_size=pick_size, index_blocks=index_blocks, **common)
+    if pick_shape == "Polygon":
+        return _picked_polygonal_locs(**common)
+    by_size = _picked_rectangular_locs if pick_shape == "Rectangle" else _picked_square_locs
+    return by_size(pick_size=pick_size, **common)
+
+
+def remove_locs_in_picks(locs: pd.DataFrame, info: list[dict], *, picks: list[tuple],
+                         pick_shape: Literal["Circle", "Rectangle", "Polygon", "Square"],
+                         pick_size: float | None = None, index_blocks: tuple = None) -> pd.DataFrame:
+    """Drop the localizations inside the picks from ``locs`` itself and return it (postprocess.py:739-799).  For
+    circles ``pick_size`` is the DIAMETER here and is halved (an integer diameter gives a float radius); for the other
+    shapes ``index_blocks`` is ignored.  Overlapping picks name a row twice, which ``drop`` takes."""
+    assert pick_shape in PICK_SHAPES, "pick_shape must be one of 'Circle', 'Rectangle', 'Polygon', or 'Square'."
+    assert pick_shape == "Polygon" or isinstance(pick_size, (int, float)), "pick_size must be a number."
+    circle = pick_shape == "Circle"
+    inside = picked_locs(locs=locs, info=info, picks=picks, pick_shape=pick_shape,
+                         pick_size=pick_size / 2 if circle else pick_size, add_group=False,
+                         index_blocks=index_blocks if circle else None)
+    locs.drop(index=np.concatenate([frame.index for frame in inside]), inplace=True)
+    return locs
