@@ -72,6 +72,7 @@
  *                      _picked_polygonal_locs, _picked_square_locs (:375-473 picked_locs), :849-928
  *                      _get_block_locs_at_numba, _locs_at_numba, picasso/lib.py:1884-2004 check_if_in_polygon,
  *                      check_if_in_rectangle
+ *   pmi_fiducials_*    picasso/postprocess.py:3062-3156 undrift_from_picked, _undrift_from_picked_coordinate
  */
 #ifndef PICASSO_HIP_H
 #define PICASSO_HIP_H
@@ -932,6 +933,37 @@ int pmi_picks_shape_dev(const void *d_x, int x_type, const void *d_y, int y_type
                         const int32_t *d_corner_offsets, const double *d_corner_x, const double *d_corner_y,
                         int64_t n_corners, int64_t n_picks, int64_t *d_offsets, int32_t *d_members, int64_t capacity,
                         int64_t *total, void *stream);
+
+/* ---- fiducial undrift (picasso/postprocess.py:3062-3156 undrift_from_picked, _undrift_from_picked_coordinate,
+ *      csrc/fiducials.hip, csrc/group_reduce.h) ------- *
+ * pmi_fiducials_drift_dev  the drift of n_columns (1 .. 3) coordinates from the member rows of n_picks >= 1 picks, in
+ *   the bits NumPy 2 gives the reference.  The rows come as a CSR in pick order: d_offsets[n_picks + 1] (int64, ascending,
+ *   d_offsets[0] == 0, d_offsets[n_picks] == n_rows), d_frame[n_rows] (int64) and the columns d_columns[c][n_rows] of
+ *   types[c] (PMI_LINK_F32 / PMI_LINK_F64); d_columns and types are host arrays, the pointers in d_columns device
+ *   pointers.  d_out[n_frames * n_columns] (float64, frame-major) receives the drift.  Per column, of type T:
+ *     1. mean_p = add.reduce(c[rows of pick p, in the given order]) / T(n_p) in T: NumPy's sum, an accumulator that takes
+ *        the pairwise sum of each 8192-element chunk in order, by one workgroup per pick; an empty pick has a NaN mean;
+ *     2. D[p, frame] = float64(c - mean_p), subtracted in T, into a P x Frames float64 matrix of NaN; on a repeated frame
+ *        of a pick the row latest in the given order wins, whatever the launch order; a frame f < 0 means f + n_frames;
+ *     3. m0[f] = (sum over p = 0 .. P - 1 in order, from row 0, of D or 0 for a NaN) / (number that are not NaN), 0 / 0 NaN;
+ *     4. msd_p = add.reduce over f of ((D - m0) ** 2 or 0 for a NaN) / (number that are not NaN); w_p = 1 / msd_p;
+ *     5. num[f] = sum over p in order of (D * w_p, or 0 for a NaN of D), den[f] = sum of (w_p * 1.0, or 0 for a NaN of D);
+ *        the frame has no value where no pick has it or where |num| * DBL_MIN >= |den|, else num / den;
+ *     6. a frame without a value (or with a NaN one) takes np.interp over the frames with one: the first / last value
+ *        outside them, slope * (f - f_lo) + y_lo with slope = (y_hi - y_lo) / (f_hi - f_lo) between.
+ *   Steps 2 - 6 are float64; nothing is contracted.  *status (host) is 0, or has bit 0 set when a frame lies outside
+ *   [-n_frames, n_frames) (NumPy: IndexError) and bit 1 when a column leaves no frame with a value (np.interp:
+ *   ValueError); d_out is then not to be read.  n_picks * n_frames <= pmi_fiducials_max_cells() (2^28: the matrix and
+ *   the winner table of step 2 take 12 bytes per cell of SCR_STAGE_A, shared by the columns), n_rows <= 2^31 - 2, else
+ *   PMI_ERR_ARG.  Runs on `stream` and synchronises it.
+ * pmi_fiducials_reduce_dev  step 1's sum alone: d_out[r] (of `type`) = add.reduce(d_values[d_offsets[r] .. d_offsets[r + 1]))
+ *   in `type`, one workgroup per run; what the tests hold against np.add.reduce.                                    */
+int64_t pmi_fiducials_max_cells(void);
+int pmi_fiducials_drift_dev(const int64_t *d_offsets, int64_t n_picks, const int64_t *d_frame, int64_t n_rows,
+                            const void *const *d_columns, const int *types, int n_columns, int64_t n_frames,
+                            double *d_out, int *status, void *stream);
+int pmi_fiducials_reduce_dev(const void *d_values, int type, int64_t n_values, const int64_t *d_offsets, int64_t n_runs,
+                             void *d_out, void *stream);
 
 /* ---- timing hooks for bench.py (HIP events on the given stream) ------- */
 int pmi_event_create(void **event);

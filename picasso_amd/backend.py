@@ -1133,6 +1133,86 @@ def picks_polygon(x, y, bounds, flags, corner_offsets, corner_x, corner_y):
     return _picks_shape(PICK_POLYGON, x, y, bounds, flags, corner_offsets, corner_x, corner_y)
 
 
+# ---- fiducial undrift (csrc/fiducials.hip, picasso/postprocess.py:3062-3156) ----
+def fiducials_max_cells() -> int:
+    """The largest picks x Frames matrix one call holds (12 bytes of device scratch per cell)."""
+    return int(_lib.load().pmi_fiducials_max_cells())
+
+
+def _fiducial_offsets(offsets):
+    import torch
+    if isinstance(offsets, torch.Tensor):
+        offsets = offsets.cpu().numpy()
+    offsets = np.ascontiguousarray(_index_column(offsets, "offsets"))
+    if offsets.ndim != 1 or len(offsets) < 1 or offsets[0] != 0 or (np.diff(offsets) < 0).any():
+        raise ValueError("offsets must be the P + 1 ascending offsets of the member rows, from 0")
+    return offsets
+
+
+def fiducials_drift(offsets, frame, columns, n_frames: int) -> np.ndarray:
+    """The drift of the picked fiducials, as the reference's ``undrift_from_picked`` computes it under NumPy 2, bit for
+    bit (pmi_fiducials_drift_dev) -> float64 (n_frames, len(columns)).  The members of the P picks come as a CSR: int64
+    ``offsets[P + 1]``, and ``frame`` and one to three float32 / float64 coordinate ``columns`` gathered into pick
+    order (host arrays or device tensors; the order inside a pick decides the bits of its mean and which row of a
+    repeated frame counts: the last).  IndexError for a frame outside [-n_frames, n_frames), ValueError when a column
+    leaves no frame with a value (np.interp), MemoryError beyond ``fiducials_max_cells()`` cells."""
+    import torch
+    _lib.require_gpu()
+    offsets = _fiducial_offsets(offsets)
+    P, F = len(offsets) - 1, int(n_frames)
+    if not 1 <= len(columns) <= 3:
+        raise ValueError("one to three coordinate columns")
+    if P == 0 or F < 1:
+        raise ValueError("array of sample points is empty")          # np.interp over no frame at all
+    if P * F > fiducials_max_cells():
+        raise MemoryError(f"{P} picks x {F} frames: more than {fiducials_max_cells()} cells in one call")
+    if isinstance(frame, torch.Tensor):
+        if frame.dtype != torch.int64 or frame.dim() != 1 or not frame.is_cuda:
+            raise TypeError("a device frame column must be a 1-D int64 tensor on the GPU")
+        d_frame = frame.contiguous()
+    else:
+        d_frame = _to_device(_index_column(frame, "frame"))
+    cols = [_pick_column(c) for c in columns]
+    M = int(offsets[-1])
+    if len(d_frame) != M or any(len(d) != M for d, _ in cols):
+        raise ValueError("frame and the columns must have offsets[-1] rows")
+    device = d_frame.device
+    d_off = _to_device(offsets)
+    out = torch.empty((F, len(cols)), dtype=torch.float64, device=device)
+    ptrs = (ctypes.c_void_p * len(cols))(*[d.data_ptr() if M else None for d, _ in cols])
+    types = (ctypes.c_int * len(cols))(*[t for _, t in cols])
+    status = ctypes.c_int(0)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    with _lib.lock():
+        _lib.check(_lib.load().pmi_fiducials_drift_dev(_dptr(d_off), P, _dptr(d_frame) if M else None, M, ptrs, types,
+                                                       len(cols), F, _dptr(out), ctypes.byref(status), stream),
+                   "pmi_fiducials_drift_dev")
+        if status.value & 1:
+            raise IndexError(f"a frame is out of bounds for {F} frames")
+        if status.value & 2:
+            raise ValueError("array of sample points is empty")
+        return out.cpu().numpy()
+
+
+def fiducials_reduce(values, offsets) -> np.ndarray:
+    """np.add.reduce of each run values[offsets[r] : offsets[r + 1]] in the values' own float type, by the workgroup
+    sum of csrc/group_reduce.h (pmi_fiducials_reduce_dev); for the tests of that sum."""
+    import torch
+    _lib.require_gpu()
+    offsets = _fiducial_offsets(offsets)
+    d_v, t = _pick_column(values)
+    if offsets[-1] > len(d_v):
+        raise ValueError("offsets run past the values")
+    R = len(offsets) - 1
+    out = torch.zeros(max(R, 1), dtype=d_v.dtype, device=d_v.device)
+    d_off = _to_device(offsets)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(d_v.device).cuda_stream)
+    with _lib.lock():
+        _lib.check(_lib.load().pmi_fiducials_reduce_dev(_dptr(d_v) if len(d_v) else None, t, len(d_v), _dptr(d_off), R,
+                                                        _dptr(out), stream), "pmi_fiducials_reduce_dev")
+        return out[:R].cpu().numpy()
+
+
 # ---- nearest-neighbour distances (csrc/knn.hip, picasso/postprocess.py:3704-3739, picasso/spinna.py:696-747) ----
 class _KnnGrid(ctypes.Structure):
     _fields_ = [("lo", ctypes.c_double * 2), ("w", ctypes.c_double * 2), ("n", ctypes.c_int32 * 2)]

@@ -8,7 +8,8 @@ pair correlation (:37-204 the index blocks, :1582-1631 ``compute_local_density``
 (:1920-2004 ``compute_dark_times`` / ``dark_times`` / ``_dark_times``, :3580-3649 ``groupprops``) on top of
 csrc/kinetics.hip, and the nearest-neighbour distances (:3704-3739 ``nn_analysis``) on top of csrc/knn.hip, and the
 cluster combine and its nearest-cluster distances (:2174-2288 ``cluster_combine``, :2291-2419 ``cluster_combine_dist``)
-on top of csrc/combine.hip.
+on top of csrc/combine.hip, and the picked localizations (:207-473) on top of csrc/picks.hip and the fiducial undrift
+from them (:2964-3156 ``undrift_from_fiducials``, ``undrift_from_picked``) on top of csrc/fiducials.hip.
 """
 from __future__ import annotations
 
@@ -841,8 +842,8 @@ def _frc(locs1: pd.DataFrame, locs2: pd.DataFrame, pixelsize: float, lp: float, 
 
 
 # ---- picked localizations (postprocess.py:207-473, :739-799) --------------------------------------------------
-# Not rebound by localize.install(): the reference's picks family (pick_similar, the fiducial undrifts, the pick
-# kinetics) hands picked_locs a K x L ``index_blocks`` tuple, which this module does not build.
+# Not rebound by localize.install(): the reference's picks family (pick_similar, the pick kinetics) hands picked_locs
+# a K x L ``index_blocks`` tuple, which this module does not build.
 PICK_NAMES = ("picked_locs", "_picked_circular_locs", "_picked_rectangular_locs", "_picked_polygonal_locs",
               "_picked_square_locs", "remove_locs_in_picks")
 
@@ -891,12 +892,9 @@ def _keeps_float32(v) -> bool:
     return isinstance(v, (bool, int, np.integer, np.bool_, np.float32, np.float16))
 
 
-def _picked_circular_locs(locs: pd.DataFrame, info: list[dict], picks: list[tuple], pick_size: float,
-                          index_blocks: tuple | None, add_group: bool,
-                          callback: Callable[[int], None] | Literal["console"] | None, progress: tqdm | None) -> list[pd.DataFrame]:
-    """Circular picks (postprocess.py:207-253): the sanity-filtered table in block order, the nine blocks around each
-    pick, ``dx**2 + dy**2 < r**2`` as numba types it; all picks in one device call."""
-    _refuse_index_blocks(index_blocks)
+def _circle_members(locs: pd.DataFrame, info: list[dict], picks: list[tuple], pick_size: float):
+    """-> (the sanity-filtered table, offsets, rows): the members of circular picks as positions in that table, in the
+    reference's order before its sort by frame; all picks in one device call."""
     locs = lib.ensure_sanity(locs, info)
     x_index = np.uint32(locs["x"].to_numpy() / pick_size)
     y_index = np.uint32(locs["y"].to_numpy() / pick_size)
@@ -916,6 +914,16 @@ def _picked_circular_locs(locs: pd.DataFrame, info: list[dict], picks: list[tupl
         r2 = float(np.float64(pick_size) * np.float64(pick_size))
     offsets, rows = backend.picks_circle(table, locs["x"].to_numpy(), locs["y"].to_numpy(), [float(x) for x, _ in picks],
                                          [float(y) for _, y in picks], block_x, block_y, flags, r2)
+    return locs, offsets, rows
+
+
+def _picked_circular_locs(locs: pd.DataFrame, info: list[dict], picks: list[tuple], pick_size: float,
+                          index_blocks: tuple | None, add_group: bool,
+                          callback: Callable[[int], None] | Literal["console"] | None, progress: tqdm | None) -> list[pd.DataFrame]:
+    """Circular picks (postprocess.py:207-253): the sanity-filtered table in block order, the nine blocks around each
+    pick, ``dx**2 + dy**2 < r**2`` as numba types it; all picks in one device call."""
+    _refuse_index_blocks(index_blocks)
+    locs, offsets, rows = _circle_members(locs, info, picks, pick_size)
     return _pick_frames(locs, offsets, rows, range(len(picks)), add_group, callback, progress, len(picks))
 
 
@@ -1010,3 +1018,81 @@ def remove_locs_in_picks(locs: pd.DataFrame, info: list[dict], *, picks: list[tu
                          index_blocks=index_blocks if circle else None)
     locs.drop(index=np.concatenate([frame.index for frame in inside]), inplace=True)
     return locs
+
+
+# ---- fiducial undrift (postprocess.py:2964-3156) ----------------------------------------------------------------
+# Not rebound by localize.install(), like the picks they are built on.
+FIDUCIAL_NAMES = ("undrift_from_fiducials", "undrift_from_picked", "_undrift_from_picked_coordinate")
+
+
+def _picked_csr(picked_locs: list[pd.DataFrame], names):
+    """The frames of ``picked_locs`` as one CSR: offsets, the frame column and the coordinate columns in pick order.  A
+    coordinate must have one dtype in all picks (as the columns of one table have): the mean of a pick is taken in it."""
+    offsets = np.zeros(len(picked_locs) + 1, np.int64)
+    offsets[1:] = np.cumsum([len(locs) for locs in picked_locs])
+
+    def column(name):
+        parts = [locs[name].to_numpy() for locs in picked_locs]
+        if len({p.dtype for p in parts}) > 1:
+            raise TypeError(f"column {name!r} has the dtypes {sorted({str(p.dtype) for p in parts})} among the picks; "
+                            "the drift takes one float32 or float64 column")
+        return np.concatenate(parts) if parts else np.zeros(0, np.float64)
+
+    return offsets, column("frame"), [column(name) for name in names]
+
+
+def _drift_from_picked(picked_locs: list[pd.DataFrame], info, names) -> np.ndarray:
+    offsets, frame, columns = _picked_csr(picked_locs, names)
+    return backend.fiducials_drift(offsets, frame, columns, info[0]["Frames"])
+
+
+def _undrift_from_picked_coordinate(picked_locs: list[pd.DataFrame], info: list[dict],
+                                    coordinate: Literal["x", "y", "z"]) -> lib.FloatArray1D:
+    """The drift of one coordinate over all frames (postprocess.py:3098-3156): every pick minus its own mean, the mean
+    over the picks weighted by the inverse of each pick's mean square deviation, frames without a localization
+    interpolated; one device call, equal to the reference under NumPy 2 in every bit."""
+    return np.ascontiguousarray(_drift_from_picked(picked_locs, info, [coordinate])[:, 0])
+
+
+def undrift_from_picked(picked_locs: list[pd.DataFrame], info: list[dict]) -> pd.DataFrame:
+    """The drift (not the undrifted localizations) from picked localizations (postprocess.py:3062-3095): a frame with
+    ``x``, ``y`` and, if every pick has it, ``z``; all coordinates in one device call."""
+    names = ["x", "y"] + (["z"] if all("z" in locs.columns for locs in picked_locs) else [])
+    drift = _drift_from_picked(picked_locs, info, names)
+    return pd.DataFrame({name: drift[:, k] for k, name in enumerate(names)})
+
+
+def undrift_from_fiducials(locs: pd.DataFrame, info: list[dict], picks: list[tuple] | None = None,
+                           pick_size: float | None = None, undrift_z: bool = True,
+                           index_blocks: tuple | None = None) -> tuple[pd.DataFrame, list[dict], pd.DataFrame]:
+    """Undrift by picked fiducial markers (postprocess.py:2964-3059) -> (undrifted copy, info with one more entry,
+    drift).  ``picks`` are (x, y) centres and ``pick_size`` the pick radius in camera pixels.  The members of the
+    circular picks come from the device as row numbers; no per-pick frame is built: the host orders each pick's rows
+    as the reference's quicksort by frame does (the order decides the bits of a pick's mean, and which of two rows of
+    one frame counts), gathers frame, x, y (, z) and makes one device call.  ``picks=None`` (``find_fiducials``) and a
+    non-None ``index_blocks`` are refused."""
+    from . import __version__
+    locs = locs.copy()
+    pixelsize = lib.get_from_metadata(info, "Pixelsize", raise_error=True)
+    if picks is None:
+        raise NotImplementedError("picks=None: find_fiducials needs the 'smooth' render, which has no kernel; pass the picks")
+    if pick_size is None:
+        raise ValueError("pick_size (radius in camera pixels) must be provided when picks are given as a list of "
+                         "coordinates.")
+    pick_radius = pick_size
+    if len(picks) == 0:
+        raise ValueError("No picks found for drift correction.")
+    _refuse_index_blocks(index_blocks)
+    sane, offsets, rows = _circle_members(locs, info, picks, pick_radius)
+    frame = sane["frame"].to_numpy()
+    for a, b in zip(offsets[:-1], offsets[1:]):          # sort_values(by="frame", kind="quicksort") of the pick's subset
+        rows[a:b] = rows[a:b][np.argsort(frame[rows[a:b]], kind="quicksort")]
+    names = ["x", "y"] + (["z"] if "z" in sane.columns else [])
+    values = backend.fiducials_drift(offsets, frame[rows], [sane[name].to_numpy()[rows] for name in names], info[0]["Frames"])
+    drift = pd.DataFrame({name: values[:, k] for k, name in enumerate(names)})
+    if not undrift_z:
+        drift = drift.drop(columns="z", errors="ignore")
+    locs = apply_drift(locs, info, drift=drift)
+    new_info = info + [{"Generated by": f"Picasso v{__version__} Undrift from picked", "Number of picks": len(picks),
+                        "Pick radius (nm)": pick_radius * pixelsize}]
+    return locs, new_info, drift
