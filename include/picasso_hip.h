@@ -73,6 +73,8 @@
  *                      _get_block_locs_at_numba, _locs_at_numba, picasso/lib.py:1884-2004 check_if_in_polygon,
  *                      check_if_in_rectangle
  *   pmi_fiducials_*    picasso/postprocess.py:3062-3156 undrift_from_picked, _undrift_from_picked_coordinate
+ *   pmi_similar_*      picasso/postprocess.py:476-736 pick_similar, _pick_similar, :820-845 _n_block_locs_at, :848-957
+ *                      get_block_locs_at_numba, locs_at_numba, rmsd_at_com
  */
 #ifndef PICASSO_HIP_H
 #define PICASSO_HIP_H
@@ -964,6 +966,42 @@ int pmi_fiducials_drift_dev(const int64_t *d_offsets, int64_t n_picks, const int
                             double *d_out, int *status, void *stream);
 int pmi_fiducials_reduce_dev(const void *d_values, int type, int64_t n_values, const int64_t *d_offsets, int64_t n_runs,
                              void *d_out, void *stream);
+
+/* ---- pick similar (picasso/postprocess.py:597-736 _pick_similar, :820-845 _n_block_locs_at, :848-957
+ *      get_block_locs_at_numba, locs_at_numba, rmsd_at_com; csrc/similar.hip) ------- *
+ * pmi_similar_shift_dev  the mean shift of every point of pick_similar's hexagonal grid, one lane per point, in the bits
+ *   numba gives the reference.  d_x / d_y are the sanity-filtered table's columns, float32 or float64 (PMI_LINK_F32 /
+ *   PMI_LINK_F64, each on its own); d_rows / d_keys / p / K / L are what pmi_pairs_order_dev returned for blocks of the
+ *   pick radius.  The grid comes as the host built it: column i lies at d_grid_x[i] in block column d_block_x[i]
+ *   (i < n_x); its n_y points lie at d_grid_y_base[j] in block row d_block_y_base[j] when i is even and at
+ *   d_grid_y_shift[j], d_block_y_shift[j] when i is odd.  Point i * n_y + j (the reference's loop order) writes
+ *   d_out_x, d_out_y (float64), d_out_n (int32) and d_out_rmsd (float64):
+ *     1. the gate: the rows of the blocks k = by - 1 .. by + 1, l = bx - 1 .. bx + 1 with 0 < k < K and 0 < l < L (block
+ *        row 0 and block column 0 never count; no such block: 0) must number >= gate, else n = 0;
+ *     2. the point's rows are those of the same blocks with 0 <= k < K, 0 <= l < L, k outside l, positions < p, gathered
+ *        once in the columns' common type S (float32 only when both are) and not taken again as the centre moves;
+ *     3. members of a centre c (float64): (S - c.x) ** 2 + (S - c.y) ** 2 < r2 in float64, strict; their mean is
+ *        float64(sum in S, in block order, from S(0)) / n.  At most one member around the grid point: n = 0;
+ *     4. the centre moves to the mean; while |dx| > 1e-3 or |dy| > 1e-3, at most max_shifts times (the reference: 500;
+ *        at most 65536), the members are taken around the new centre; at most one member ends the loop;
+ *     5. n is the size of the last set, (out_x, out_y) its mean (the mean before it when n <= 1) and out_rmsd =
+ *        sqrt(sum in order of ((S - out_x) ** 2 + (S - out_y) ** 2) / n), 0 when n <= 1.  A skipped point (n = 0 from
+ *        step 1 or 3) writes the grid point and 0.
+ *   Nothing is contracted; the divisions and the square root are correctly rounded.  The gathered columns take 2 p
+ *   values of SCR_STAGE_A.  n_x * n_y <= 2^31 - 2.  Runs on `stream` and synchronises it.
+ * pmi_similar_filter     the reference's greedy pass, on the host, over host arrays: candidate i (in grid order) gets
+ *   keep[i] = 1 when every given pick and every earlier kept candidate q has (q.x - x) ** 2 + (q.y - y) ** 2 > d2 in
+ *   float64, uncontracted, else 0.  `cell` is the pick diameter d: the picks are held on a uniform grid of cells a
+ *   little wider than it and a candidate looks at the 3 x 3 cells around its own (any cell is correct when cell is not
+ *   positive; the given picks may lie closer together than d and are all checked).  Non-finite input: PMI_ERR_ARG.  */
+int pmi_similar_shift_dev(const void *d_x, int x_type, const void *d_y, int y_type, const int32_t *d_rows,
+                          const uint64_t *d_keys, int64_t n, int64_t p, int64_t K, int64_t L, const double *d_grid_x,
+                          const int64_t *d_block_x, int64_t n_x, const double *d_grid_y_base,
+                          const double *d_grid_y_shift, const int64_t *d_block_y_base, const int64_t *d_block_y_shift,
+                          int64_t n_y, double r2, double gate, int64_t max_shifts, double *d_out_x, double *d_out_y,
+                          int32_t *d_out_n, double *d_out_rmsd, void *stream);
+int pmi_similar_filter(const double *cand_x, const double *cand_y, int64_t n_candidates, const double *pick_x,
+                       const double *pick_y, int64_t n_picks, double d2, double cell, uint8_t *keep);
 
 /* ---- timing hooks for bench.py (HIP events on the given stream) ------- */
 int pmi_event_create(void **event);

@@ -159,6 +159,9 @@ SYMBOLS = {
     "pmi_fiducials_max_cells": (_i64, []),
     "pmi_fiducials_drift_dev": (_i32, [_p, _i64, _p, _i64, _p, _p, _i32, _i64, _p, _p, _p]),
     "pmi_fiducials_reduce_dev": (_i32, [_p, _i32, _i64, _p, _i64, _p, _p]),
+    "pmi_similar_shift_dev": (_i32, [_p, _i32, _p, _i32, _p, _p, _i64, _i64, _i64, _i64, _p, _p, _i64, _p, _p, _p, _p, _i64,
+                                     _f64, _f64, _i64, _p, _p, _p, _p, _p]),
+    "pmi_similar_filter": (_i32, [_p, _p, _i64, _p, _p, _i64, _f64, _f64, _p]),
     "pmi_event_create": (_i32, [_p]),
     "pmi_event_record": (_i32, [_p, _p]),
     "pmi_event_elapsed_ms": (_i32, [_p, _p, _p]),

@@ -1133,6 +1133,64 @@ def picks_polygon(x, y, bounds, flags, corner_offsets, corner_x, corner_y):
     return _picks_shape(PICK_POLYGON, x, y, bounds, flags, corner_offsets, corner_x, corner_y)
 
 
+# ---- pick similar (csrc/similar.hip, picasso/postprocess.py:476-736, :820-957) ----
+SIMILAR_MAX_SHIFTS = 500          # the reference's cap on the moves of one grid point
+
+
+def _grid_blocks(a):
+    """Block indices of grid points as the kernel takes them: int64, clipped so that index + 1 cannot overflow (any
+    index beyond [-1, 2^32] names no block of the grid)."""
+    return np.clip(_index_column(a, "block indices"), -2, 1 << 33)
+
+
+def similar_shift(table: "BlockTable", x, y, x_range, y_range_base, y_range_shift, x_block, y_block_base, y_block_shift,
+                  r2: float, gate: float, max_shifts: int = SIMILAR_MAX_SHIFTS):
+    """The mean shift of every point of pick_similar's grid over a table in block order (``table`` built from
+    uint32(x / r), uint32(y / r) of the same rows; host arrays or device tensors) -> (cx, cy float64, n int32, rmsd
+    float64) per grid point, columns outside and y inside, odd columns on ``y_range_shift`` (pmi_similar_shift_dev).
+    ``gate`` is the reference's ``min_n_locs``; ``n == 0`` marks a point the gate or the first circle skipped."""
+    import torch
+    _lib.require_gpu()
+    d_x, tx = _pick_column(x)
+    d_y, ty = _pick_column(y)
+    if len(d_x) != table.n or len(d_y) != table.n:
+        raise ValueError("x and y must have one entry per row of the table")
+    gx, gb, gs = (np.ascontiguousarray(a, np.float64) for a in (x_range, y_range_base, y_range_shift))
+    bx, bb, bs = (np.ascontiguousarray(_grid_blocks(a)) for a in (x_block, y_block_base, y_block_shift))
+    n_x, n_y = len(gx), len(gb)
+    if len(bx) != n_x or not (len(gs) == len(bb) == len(bs) == n_y) or any(a.ndim != 1 for a in (gx, gb, gs, bx, bb, bs)):
+        raise ValueError("one block index per grid value, and as many shifted y values as base ones")
+    if not 0 <= int(max_shifts) <= 1 << 16:
+        raise ValueError("max_shifts must lie in 0 .. 65536")
+    G = n_x * n_y
+    if G == 0:
+        return np.zeros(0), np.zeros(0), np.zeros(0, np.int32), np.zeros(0)
+    d_grid = [_to_device(a) for a in (gx, bx, gb, gs, bb, bs)]
+    out = torch.zeros(3 * G, dtype=torch.float64, device=table.device)
+    out_n = torch.zeros(G, dtype=torch.int32, device=table.device)
+    with _lib.lock():
+        _lib.check(_lib.load().pmi_similar_shift_dev(
+            _dptr(d_x), tx, _dptr(d_y), ty, _dptr(table.rows), _dptr(table.keys), table.n, table.p, table.K, table.L,
+            _dptr(d_grid[0]), _dptr(d_grid[1]), n_x, _dptr(d_grid[2]), _dptr(d_grid[3]), _dptr(d_grid[4]), _dptr(d_grid[5]),
+            n_y, float(r2), float(gate), int(max_shifts), _dptr(out[:G]), _dptr(out[G:2 * G]), _dptr(out_n),
+            _dptr(out[2 * G:]), ctypes.c_void_p(table.stream)), "pmi_similar_shift_dev")
+        host = out.cpu().numpy()
+        return host[:G].copy(), host[G:2 * G].copy(), out_n.cpu().numpy(), host[2 * G:].copy()
+
+
+def similar_filter(cand_x, cand_y, pick_x, pick_y, d2: float, d: float) -> np.ndarray:
+    """The greedy pass of pick_similar over candidates in grid order, on the host (pmi_similar_filter) -> bool mask: a
+    candidate is kept when every given pick and every earlier kept candidate has dx * dx + dy * dy > d2."""
+    cx, cy = np.ascontiguousarray(cand_x, np.float64), np.ascontiguousarray(cand_y, np.float64)
+    px, py = np.ascontiguousarray(pick_x, np.float64), np.ascontiguousarray(pick_y, np.float64)
+    if cx.shape != cy.shape or px.shape != py.shape or cx.ndim != 1 or px.ndim != 1:
+        raise ValueError("one x and one y per candidate and per pick")
+    keep = np.zeros(len(cx), np.uint8)
+    _lib.check(_lib.load().pmi_similar_filter(_lib.ptr(cx), _lib.ptr(cy), len(cx), _lib.ptr(px), _lib.ptr(py), len(px),
+                                              float(d2), float(d), _lib.ptr(keep)), "pmi_similar_filter")
+    return keep.astype(bool)
+
+
 # ---- fiducial undrift (csrc/fiducials.hip, picasso/postprocess.py:3062-3156) ----
 def fiducials_max_cells() -> int:
     """The largest picks x Frames matrix one call holds (12 bytes of device scratch per cell)."""

@@ -9,7 +9,8 @@ pair correlation (:37-204 the index blocks, :1582-1631 ``compute_local_density``
 csrc/kinetics.hip, and the nearest-neighbour distances (:3704-3739 ``nn_analysis``) on top of csrc/knn.hip, and the
 cluster combine and its nearest-cluster distances (:2174-2288 ``cluster_combine``, :2291-2419 ``cluster_combine_dist``)
 on top of csrc/combine.hip, and the picked localizations (:207-473) on top of csrc/picks.hip and the fiducial undrift
-from them (:2964-3156 ``undrift_from_fiducials``, ``undrift_from_picked``) on top of csrc/fiducials.hip.
+from them (:2964-3156 ``undrift_from_fiducials``, ``undrift_from_picked``) on top of csrc/fiducials.hip, and
+``pick_similar`` (:476-736) on top of csrc/similar.hip.
 """
 from __future__ import annotations
 
@@ -892,9 +893,10 @@ def _keeps_float32(v) -> bool:
     return isinstance(v, (bool, int, np.integer, np.bool_, np.float32, np.float16))
 
 
-def _circle_members(locs: pd.DataFrame, info: list[dict], picks: list[tuple], pick_size: float):
+def _circle_members(locs: pd.DataFrame, info: list[dict], picks: list[tuple], pick_size: float, with_table: bool = False):
     """-> (the sanity-filtered table, offsets, rows): the members of circular picks as positions in that table, in the
-    reference's order before its sort by frame; all picks in one device call."""
+    reference's order before its sort by frame; all picks in one device call.  ``with_table`` appends the
+    backend.BlockTable the call ordered the rows with."""
     locs = lib.ensure_sanity(locs, info)
     x_index = np.uint32(locs["x"].to_numpy() / pick_size)
     y_index = np.uint32(locs["y"].to_numpy() / pick_size)
@@ -914,7 +916,7 @@ def _circle_members(locs: pd.DataFrame, info: list[dict], picks: list[tuple], pi
         r2 = float(np.float64(pick_size) * np.float64(pick_size))
     offsets, rows = backend.picks_circle(table, locs["x"].to_numpy(), locs["y"].to_numpy(), [float(x) for x, _ in picks],
                                          [float(y) for _, y in picks], block_x, block_y, flags, r2)
-    return locs, offsets, rows
+    return (locs, offsets, rows, table) if with_table else (locs, offsets, rows)
 
 
 def _picked_circular_locs(locs: pd.DataFrame, info: list[dict], picks: list[tuple], pick_size: float,
@@ -1096,3 +1098,77 @@ def undrift_from_fiducials(locs: pd.DataFrame, info: list[dict], picks: list[tup
     new_info = info + [{"Generated by": f"Picasso v{__version__} Undrift from picked", "Number of picks": len(picks),
                         "Pick radius (nm)": pick_radius * pixelsize}]
     return locs, new_info, drift
+
+
+# ---- pick similar (postprocess.py:476-736, :820-957) -------------------------------------------------------------
+# Not rebound by localize.install(), like the picks it is built on.
+SIMILAR_NAMES = ("pick_similar",)
+
+
+def _sequential_mean(values: np.ndarray) -> np.float64:
+    """numba's ``np.mean`` of a 1-D float array: ``c = dtype(0); for v in a: c += v`` in the array's own type (one
+    sequential chain, which np.add.accumulate walks too), then a float64 division; an empty array divides by zero."""
+    if values.size == 0:
+        raise ZeroDivisionError("division by zero")
+    total = np.add.accumulate(np.concatenate([np.zeros(1, values.dtype), values]))[-1]
+    return np.float64(total) / np.float64(values.size)
+
+
+def _rmsd_at_com(xs: np.ndarray, ys: np.ndarray) -> np.float64:
+    """``rmsd_at_com`` (postprocess.py:947-957) as numba types it: float64 deviations from the two means, plain
+    products, the sequential mean of their sum, a correctly rounded square root."""
+    ex, ey = xs.astype(np.float64) - _sequential_mean(xs), ys.astype(np.float64) - _sequential_mean(ys)
+    return np.sqrt(_sequential_mean(ex * ex + ey * ey))
+
+
+def pick_similar(locs: pd.DataFrame, info: list[dict], picks: list[tuple], d: float, std_range: float = 2.0,
+                 index_blocks: tuple = None) -> list[tuple]:
+    """Circular picks that resemble the given ones (postprocess.py:476-594): a hexagonal grid of circles of diameter
+    ``d`` over the field of view, each shifted to the centre of mass of its members until it rests, kept when its
+    member count and RMSD lie within ``std_range`` standard deviations of the given picks' and no pick kept so far,
+    the given ones included, lies within ``d`` -> the given picks, then the found ones in grid order, as (x, y) pairs
+    equal to the reference's in every bit.  The grid search is one device call (one lane per grid point), the greedy
+    pass runs on the host.  A given pick without members raises ZeroDivisionError as numba's mean does; picks whose x or
+    y values are all integers raise TypeError (numba cannot retype the integer array the found picks are appended to
+    and refuses to compile); a non-None ``index_blocks`` is refused."""
+    _refuse_index_blocks(index_blocks)
+    r = d / 2
+    d2 = d**2
+    # n_locs and rmsd of the given picks
+    sane, offsets, rows, table = _circle_members(locs, info, picks, r, with_table=True)
+    x, y = sane["x"].to_numpy(), sane["y"].to_numpy()
+    stacked = np.result_type(x.dtype, y.dtype)          # the reference stacks x and y into one array
+    n_locs, rmsd = [], []
+    for a, b in zip(offsets[:-1], offsets[1:]):
+        n_locs.append(int(b - a))
+        rmsd.append(_rmsd_at_com(x[rows[a:b]].astype(stacked), y[rows[a:b]].astype(stacked)))
+    mean_n_locs = np.mean(n_locs)
+    mean_rmsd = np.mean(rmsd)
+    std_n_locs = np.std(n_locs)
+    std_rmsd = np.std(rmsd)
+    min_n_locs = max(2, mean_n_locs - std_range * std_n_locs)
+    max_n_locs = mean_n_locs + std_range * std_n_locs
+    min_rmsd = mean_rmsd - std_range * std_rmsd
+    max_rmsd = mean_rmsd + std_range * std_rmsd
+    x_similar = np.array([_[0] for _ in picks])
+    y_similar = np.array([_[1] for _ in picks])
+    if x_similar.dtype.kind != "f" or y_similar.dtype.kind != "f":
+        raise TypeError("the x (or y) values of the picks are all integers: the reference appends floats to that "
+                        "integer array inside a jitted loop, which numba refuses to type; pass floats")
+    # the grid, as the reference builds it
+    x_range = np.arange(d / 2, info[0]["Width"], np.sqrt(3) * d / 2)
+    y_range_base = np.arange(d / 2, info[0]["Height"] - d / 2, d)
+    y_range_shift = y_range_base + d / 2
+    x_r = np.uint64(x_range / r)
+    y_r1 = np.uint64(y_range_shift / r)
+    y_r2 = np.uint64(y_range_base / r)
+    cx, cy, n, spread = backend.similar_shift(table, x, y, x_range, y_range_base, y_range_shift, x_r, y_r2, y_r1,
+                                              float(np.float64(r) * np.float64(r)), float(min_n_locs))
+    # a candidate that fails a range is never appended and never influences another: the ranges first, then the
+    # greedy pass in grid order over the rest
+    with np.errstate(invalid="ignore"):
+        candidates = np.flatnonzero((n >= min_n_locs) & (n <= max_n_locs) & (spread >= min_rmsd) & (spread <= max_rmsd))
+    keep = backend.similar_filter(cx[candidates], cy[candidates], x_similar, y_similar, d2, d)
+    x_similar = np.concatenate([x_similar.astype(np.float64), cx[candidates][keep]])
+    y_similar = np.concatenate([y_similar.astype(np.float64), cy[candidates][keep]])
+    return list(zip(x_similar, y_similar))
