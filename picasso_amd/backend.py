@@ -955,10 +955,12 @@ class BlockTable:
         return self.rows[:self.n].cpu().numpy().astype(np.int64)
 
     def _columns(self, x, y):
-        x, y = np.asarray(x), np.asarray(y)
-        if len(x) != self.n or len(y) != self.n:
+        """x / y of the table's rows, host arrays or device tensors -> (d_x, x type code, d_y, y type code)."""
+        d_x, tx = _pick_column(x)
+        d_y, ty = _pick_column(y)
+        if len(d_x) != self.n or len(d_y) != self.n:
             raise ValueError("x and y must have one entry per row of the table")
-        return _to_device(x), link_type(x.dtype, True), _to_device(y), link_type(y.dtype, True)
+        return d_x, tx, d_y, ty
 
     def density(self, x, y, r2: float) -> np.ndarray:
         """uint32 neighbour count of every row, in block order; x / y in the caller's row order."""
@@ -1001,6 +1003,15 @@ def _pick_column(a):
     return _to_device(a), link_type(a.dtype, True)
 
 
+def _grid_blocks(a):
+    """Block indices of picks or grid points as the kernel takes them: int64, clipped so that index + 1 cannot overflow
+    (any index beyond [-1, 2^32] names no block of the grid; a Python integer too large for int64 is one of them)."""
+    a = np.asarray(a)
+    if a.dtype == object:
+        a = np.array([min(max(int(b), -2), 1 << 33) for b in a], np.int64)
+    return np.clip(_index_column(a, "block indices"), -2, 1 << 33)
+
+
 def _picks_csr(call, n_picks: int, device):
     """The two passes of a pick call: count (offsets and the total, the one copy to the host), then write."""
     import torch
@@ -1018,19 +1029,14 @@ def picks_circle(table: "BlockTable", x, y, pick_x, pick_y, block_x, block_y, fl
     same rows) -> (int64 offsets[P + 1], int64 rows): per pick the rows with dx ** 2 + dy ** 2 < r2 of the blocks around
     (block_y, block_x), in block order.  ``flags``: numba's typing of each pick, see pmi_picks_circle_dev."""
     _lib.require_gpu()
-    d_x, tx = _pick_column(x)
-    d_y, ty = _pick_column(y)
-    if len(d_x) != table.n or len(d_y) != table.n:
-        raise ValueError("x and y must have one entry per row of the table")
+    d_x, tx, d_y, ty = table._columns(x, y)
     P = len(pick_x)
     if not (len(pick_y) == len(block_x) == len(block_y) == len(flags) == P):
         raise ValueError("one coordinate pair, block pair and flag per pick")
     if P == 0:
         return np.zeros(1, np.int64), np.zeros(0, np.int64)
     d_px, d_py = _to_device(pick_x, np.float64), _to_device(pick_y, np.float64)
-    # any block index beyond [-1, 2^32] names no block of the grid: clipped so that index + 1 cannot overflow
-    d_bx = _to_device(np.array([min(max(int(b), -2), 1 << 33) for b in block_x], np.int64))
-    d_by = _to_device(np.array([min(max(int(b), -2), 1 << 33) for b in block_y], np.int64))
+    d_bx, d_by = _to_device(_grid_blocks(block_x)), _to_device(_grid_blocks(block_y))
     d_f = _to_device(flags, np.uint8)
     L = _lib.load()
     with _lib.lock():
@@ -1137,12 +1143,6 @@ def picks_polygon(x, y, bounds, flags, corner_offsets, corner_x, corner_y):
 SIMILAR_MAX_SHIFTS = 500          # the reference's cap on the moves of one grid point
 
 
-def _grid_blocks(a):
-    """Block indices of grid points as the kernel takes them: int64, clipped so that index + 1 cannot overflow (any
-    index beyond [-1, 2^32] names no block of the grid)."""
-    return np.clip(_index_column(a, "block indices"), -2, 1 << 33)
-
-
 def similar_shift(table: "BlockTable", x, y, x_range, y_range_base, y_range_shift, x_block, y_block_base, y_block_shift,
                   r2: float, gate: float, max_shifts: int = SIMILAR_MAX_SHIFTS):
     """The mean shift of every point of pick_similar's grid over a table in block order (``table`` built from
@@ -1151,10 +1151,7 @@ def similar_shift(table: "BlockTable", x, y, x_range, y_range_base, y_range_shif
     ``gate`` is the reference's ``min_n_locs``; ``n == 0`` marks a point the gate or the first circle skipped."""
     import torch
     _lib.require_gpu()
-    d_x, tx = _pick_column(x)
-    d_y, ty = _pick_column(y)
-    if len(d_x) != table.n or len(d_y) != table.n:
-        raise ValueError("x and y must have one entry per row of the table")
+    d_x, tx, d_y, ty = table._columns(x, y)
     gx, gb, gs = (np.ascontiguousarray(a, np.float64) for a in (x_range, y_range_base, y_range_shift))
     bx, bb, bs = (np.ascontiguousarray(_grid_blocks(a)) for a in (x_block, y_block_base, y_block_shift))
     n_x, n_y = len(gx), len(gb)

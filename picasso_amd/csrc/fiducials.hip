@@ -215,13 +215,7 @@ struct Work {
 template <typename Op>
 static int scan_i32(const int32_t *in, int32_t *out, size_t n, Op op, hipStream_t s)
 {
-    size_t bytes = 0;
-    PMI_HIP(rocprim::inclusive_scan(nullptr, bytes, in, out, n, op, s));
-    void *tmp = nullptr;
-    const int rc = scratch(SCR_STAGE_B, bytes + 64, &tmp);
-    if (rc != PMI_OK) return rc;
-    PMI_HIP(rocprim::inclusive_scan(tmp, bytes, in, out, n, op, s));
-    return PMI_OK;
+    return two_pass([&](void *tmp, size_t &bytes) { return rocprim::inclusive_scan(tmp, bytes, in, out, n, op, s); });
 }
 
 template <typename T>

@@ -402,13 +402,6 @@ static int nena_typed(const TX *x, const TY *y, const int64_t *frame, const int6
 
 using namespace pmi;
 
-#define PMI_LINK_DISPATCH(fn, ...)                                                                          \
-    (x_type == PMI_LINK_F32                                                                                 \
-         ? (y_type == PMI_LINK_F32 ? fn<float, float>((const float *)d_x, (const float *)d_y, __VA_ARGS__)  \
-                                   : fn<float, double>((const float *)d_x, (const double *)d_y, __VA_ARGS__)) \
-         : (y_type == PMI_LINK_F32 ? fn<double, float>((const double *)d_x, (const float *)d_y, __VA_ARGS__) \
-                                   : fn<double, double>((const double *)d_x, (const double *)d_y, __VA_ARGS__)))
-
 extern "C" {
 
 int pmi_link_frame_index_dev(const int64_t *d_frame, int64_t n, int64_t k, int32_t *d_lo, int32_t *d_hi, void *stream)
@@ -434,7 +427,7 @@ int pmi_link_groups_dev(const int64_t *d_frame, const void *d_x, int x_type, con
     }
     *n_groups = 0;
     if (n == 0) return PMI_OK;
-    return PMI_LINK_DISPATCH(link::groups_typed, d_frame, d_group, (int32_t)n, r2, k, d_link_group, n_groups,
+    return PMI_XY_DISPATCH(link::groups_typed, d_frame, d_group, (int32_t)n, r2, k, d_link_group, n_groups,
                              (hipStream_t)stream);
 }
 
@@ -497,7 +490,7 @@ int pmi_nena_hist_dev(const int64_t *d_frame, const void *d_x, int x_type, const
         set_error("pmi_nena_hist_dev: %d bins of %g (at most %d), or a NULL column", n_bins, bin_size, link::MAX_BINS);
         return PMI_ERR_ARG;
     }
-    return PMI_LINK_DISPATCH(link::nena_typed, d_frame, d_group, (int32_t)n, d_max, bin_size, (int32_t)n_bins,
+    return PMI_XY_DISPATCH(link::nena_typed, d_frame, d_group, (int32_t)n, d_max, bin_size, (int32_t)n_bins,
                              (unsigned long long *)d_hist, (hipStream_t)stream);
 }
 

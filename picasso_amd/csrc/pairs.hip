@@ -6,6 +6,8 @@
 // y_index << 32 | x_index, and (key, row) is sorted with the stable radix sort on the bits the largest indices need (the
 // x bits, then the y bits): the permutation is np.lexsort([x_index, y_index]).  There is no K x L table of block starts
 // and ends: the rows of a block are two bisections of the sorted keys, so memory is O(rows) for any frame and radius.
+// This source makes the order; reading it (the key, a run of blocks, the clamped 3 x 3 window) is rows_blocks.h, shared
+// with picks.hip and similar.hip.
 //
 // The fill stall.  The reference fills its table by walking the sorted rows block by block, and stops for good at the
 // first sorted row whose index lies outside the K x L grid: every later block starts and ends there.  p = that position
@@ -29,7 +31,7 @@
 // row count.
 #include <algorithm>
 
-#include "rows_common.h"
+#include "rows_blocks.h"
 
 #pragma clang fp contract(off)
 
@@ -39,19 +41,9 @@ namespace pairs {
 using namespace rows;
 
 constexpr int MAX_LDS_BINS = 8192;       // 32 KB of LDS
-constexpr int64_t INDEX_MAX = 0xffffffffLL;
 
 __device__ __forceinline__ float sqrt_rn(float a) { return __builtin_sqrtf(a); }
 __device__ __forceinline__ double sqrt_rn(double a) { return __builtin_sqrt(a); }
-
-// the sorted keys, the visible prefix and the grid
-struct Blocks {
-    const uint64_t *keys;
-    int32_t n, p;
-    int64_t K, L;
-};
-
-__device__ __forceinline__ uint64_t block_key(int64_t k, int64_t l) { return ((uint64_t)k << 32) | (uint64_t)l; }
 
 // keys, the identity permutation and the largest x / y index (one atomic per block and axis)
 __global__ void key_kernel(const uint32_t *__restrict__ x_index, const uint32_t *__restrict__ y_index, int32_t n,
@@ -116,13 +108,6 @@ struct Pair {
     }
 };
 
-// visible rows of the blocks (k, l0 .. l1), all inside the grid: positions [a, b)
-__device__ __forceinline__ void block_run(const Blocks &g, int64_t k, int64_t l0, int64_t l1, int32_t *a, int32_t *b)
-{
-    *a = lower_bound(g.keys, 0, g.p, block_key(k, l0));
-    *b = lower_bound(g.keys, *a, g.p, block_key(k, l1) + 1u);
-}
-
 template <typename TX, typename TY>
 __device__ __forceinline__ uint32_t count_run(const TX *__restrict__ xs, const TY *__restrict__ ys, int32_t a, int32_t b,
                                               TX cx, TY cy, double r2)
@@ -145,6 +130,7 @@ __global__ void density_kernel(Blocks g, const TX *__restrict__ xs, const TY *__
     const int64_t ki = (int64_t)(key >> 32), li = (int64_t)(key & 0xffffffffu);
     const TX cx = xs[i];
     const TY cy = ys[i];
+    const Window w = window(g, ki, li);                             // its column span; the block rows wrap here
     uint32_t c = 0;
     for (int64_t k = ki - 1; k <= ki + 1; ++k) {
         const int64_t kk = k < 0 ? k + g.K : k;                     // -1 is the last block row
@@ -154,9 +140,8 @@ __global__ void density_kernel(Blocks g, const TX *__restrict__ xs, const TY *__
             block_run(g, kk, g.L - 1, g.L - 1, &a, &b);
             c += count_run(xs, ys, a, b, cx, cy, r2);
         }
-        const int64_t l0 = li > 0 ? li - 1 : 0, l1 = std::min(std::min(li + 1, g.L - 1), INDEX_MAX);
-        if (l0 > l1) continue;
-        block_run(g, kk, l0, l1, &a, &b);
+        if (w.l0 > w.l1) continue;
+        block_run(g, kk, w.l0, w.l1, &a, &b);
         c += count_run(xs, ys, a, b, cx, cy, r2);
     }
     density[i] = c;
@@ -301,13 +286,6 @@ static int hist_typed(const TX *x, const TY *y, const int32_t *rows, Blocks g, d
 
 using namespace pmi;
 
-#define PMI_PAIRS_DISPATCH(fn, ...)                                                                          \
-    (x_type == PMI_LINK_F32                                                                                  \
-         ? (y_type == PMI_LINK_F32 ? fn<float, float>((const float *)d_x, (const float *)d_y, __VA_ARGS__)   \
-                                   : fn<float, double>((const float *)d_x, (const double *)d_y, __VA_ARGS__)) \
-         : (y_type == PMI_LINK_F32 ? fn<double, float>((const double *)d_x, (const float *)d_y, __VA_ARGS__) \
-                                   : fn<double, double>((const double *)d_x, (const double *)d_y, __VA_ARGS__)))
-
 extern "C" {
 
 int pmi_pairs_order_dev(const uint32_t *d_x_index, const uint32_t *d_y_index, int64_t n, int64_t K, int64_t L,
@@ -335,8 +313,8 @@ int pmi_pairs_density_dev(const void *d_x, int x_type, const void *d_y, int y_ty
         return PMI_ERR_ARG;
     }
     if (n == 0) return PMI_OK;
-    const pairs::Blocks g{d_keys, (int32_t)n, (int32_t)p, K, L};
-    return PMI_PAIRS_DISPATCH(pairs::density_typed, d_rows, g, r2, d_density, (hipStream_t)stream);
+    const rows::Blocks g{d_keys, (int32_t)n, (int32_t)p, K, L};
+    return PMI_XY_DISPATCH(pairs::density_typed, d_rows, g, r2, d_density, (hipStream_t)stream);
 }
 
 int pmi_pairs_distance_hist_dev(const void *d_x, int x_type, const void *d_y, int y_type, const int32_t *d_rows,
@@ -351,9 +329,9 @@ int pmi_pairs_distance_hist_dev(const void *d_x, int x_type, const void *d_y, in
         return PMI_ERR_ARG;
     }
     if (n_bins == 0) return PMI_OK;
-    const pairs::Blocks g{d_keys, (int32_t)n, (int32_t)p, K, L};
-    return PMI_PAIRS_DISPATCH(pairs::hist_typed, d_rows, g, r_max, r2, bin_size, (int32_t)n_bins,
-                              (unsigned long long *)d_hist, (hipStream_t)stream);
+    const rows::Blocks g{d_keys, (int32_t)n, (int32_t)p, K, L};
+    return PMI_XY_DISPATCH(pairs::hist_typed, d_rows, g, r_max, r2, bin_size, (int32_t)n_bins,
+                           (unsigned long long *)d_hist, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -4,7 +4,8 @@
 // the reference holds them in before its sort by frame.
 //
 // One workgroup per pick, all picks in one launch.  A pick walks a few runs of rows in a block order (the sorted keys of
-// pmi_pairs_order_dev: a run is two bisections, there is no K x L table), tests 256 rows at a time and compacts the
+// pmi_pairs_order_dev, read through rows_blocks.h: a run is two bisections, there is no K x L table; a circle's blocks
+// are that header's clamped 3 x 3 window), tests 256 rows at a time and compacts the
 // members in run order: a ballot per wave, the four wave counts through LDS.  The same kernel counts (members == NULL)
 // and writes; between the two the host scans the counts into offsets[P + 1] and reads the total, which sizes `members`.
 //
@@ -32,7 +33,7 @@
 #include <algorithm>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
-#include "rows_common.h"
+#include "rows_blocks.h"
 
 #pragma clang fp contract(off)
 
@@ -41,28 +42,12 @@ namespace picks {
 
 using namespace rows;
 
-constexpr int64_t INDEX_MAX = 0xffffffffLL;
 constexpr int WAVES = BLOCK / 64;
-
-struct Blocks {
-    const uint64_t *keys;
-    int32_t n, p;
-    int64_t K, L;
-};
 
 struct Grid {
     double x0, y0, x1, y1, cell;
     int64_t CX, CY;
 };
-
-__device__ __forceinline__ uint64_t block_key(int64_t k, int64_t l) { return ((uint64_t)k << 32) | (uint64_t)l; }
-
-// visible rows of the blocks (k, l0 .. l1), all inside the grid: positions [a, b)
-__device__ __forceinline__ void block_run(const Blocks &g, int64_t k, int64_t l0, int64_t l1, int32_t *a, int32_t *b)
-{
-    *a = lower_bound(g.keys, 0, g.p, block_key(k, l0));
-    *b = lower_bound(g.keys, *a, g.p, block_key(k, l1) + 1u);
-}
 
 // the cell of a coordinate inside [lo, hi]: monotone in v, so a row between two bounds lies between their cells
 __device__ __forceinline__ int64_t cell_of(double v, double lo, double cell, int64_t cells)
@@ -142,15 +127,12 @@ __global__ void circle_kernel(Blocks g, const TX *__restrict__ x, const TY *__re
     };
     const int64_t base = members ? offsets[pick] : 0;
     int64_t done = 0;
-    if (ki >= -1 && ki <= g.K && li >= -1 && li <= g.L) {          // else no block of the nine lies inside the grid
-        for (int64_t k = ki - 1; k <= ki + 1; ++k) {
-            if (k < 0 || k >= g.K || k > INDEX_MAX) continue;
-            const int64_t l0 = li > 0 ? li - 1 : 0, l1 = std::min(std::min(li + 1, g.L - 1), INDEX_MAX);
-            if (l0 > l1) continue;
-            int32_t a, b;
-            block_run(g, k, l0, l1, &a, &b);
-            walk_run(rows, g.n, a, b, test, wave_count, base, capacity, members, &done);
-        }
+    const Window w = window(g, ki, li);
+    for (int t = 0; t < 3; ++t) {
+        if (!w.row[t]) continue;
+        int32_t a, b;
+        block_run(g, ki - 1 + t, w.l0, w.l1, &a, &b);
+        walk_run(rows, g.n, a, b, test, wave_count, base, capacity, members, &done);
     }
     if (!members && threadIdx.x == 0) counts[pick] = (uint32_t)std::min<int64_t>(done, 0xffffffffLL);
 }
@@ -271,15 +253,21 @@ static int check_call(const char *what, int64_t n, int64_t p, int64_t K, int64_t
     return PMI_OK;
 }
 
-// offsets[0 .. P] from counts[0 .. P) (counts[P] is a zero the scan runs over), and the total on the host
-static int scan_counts(uint32_t *counts, int64_t P, int64_t *offsets, int64_t *total, hipStream_t s)
+// The count pass of a call: launch(counts) fills counts[0 .. P), one workgroup per pick; offsets[0 .. P] is their
+// exclusive scan (counts[P] is a zero the scan runs over), and the total comes to the host.
+template <typename Launch>
+static int count_pass(int64_t P, Launch &&launch, int64_t *offsets, int64_t *total, hipStream_t s)
 {
-    size_t bytes = 0;
-    PMI_HIP(rocprim::exclusive_scan(nullptr, bytes, counts, offsets, (int64_t)0, (size_t)P + 1, rocprim::plus<int64_t>(), s));
-    void *tmp = nullptr;
-    const int rc = scratch(SCR_STAGE_B, bytes + 64, &tmp);
+    uint32_t *counts;
+    int rc = carve(SCR_STAGE_A, [&](Arena &ar) { counts = ar.take<uint32_t>((size_t)P + 1); });
     if (rc != PMI_OK) return rc;
-    PMI_HIP(rocprim::exclusive_scan(tmp, bytes, counts, offsets, (int64_t)0, (size_t)P + 1, rocprim::plus<int64_t>(), s));
+    PMI_HIP(hipMemsetAsync(counts, 0, sizeof(uint32_t) * ((size_t)P + 1), s));
+    launch(counts);
+    PMI_HIP(hipGetLastError());
+    rc = two_pass([&](void *tmp, size_t &bytes) {
+        return rocprim::exclusive_scan(tmp, bytes, counts, offsets, (int64_t)0, (size_t)P + 1, rocprim::plus<int64_t>(), s);
+    });
+    if (rc != PMI_OK) return rc;
     int64_t h_total = 0;
     PMI_HIP(hipMemcpyAsync(&h_total, offsets + P, sizeof(int64_t), hipMemcpyDeviceToHost, s));
     PMI_HIP(hipStreamSynchronize(s));
@@ -312,14 +300,10 @@ static int circle_typed(const TX *x, const TY *y, Blocks g, const CircleArgs &c,
         PMI_HIP(hipStreamSynchronize(s));
         return PMI_OK;
     }
-    uint32_t *counts;
-    int rc = carve(SCR_STAGE_A, [&](Arena &ar) { counts = ar.take<uint32_t>((size_t)P + 1); });
-    if (rc != PMI_OK) return rc;
-    PMI_HIP(hipMemsetAsync(counts, 0, sizeof(uint32_t) * ((size_t)P + 1), s));
-    circle_kernel<TX, TY><<<P, BLOCK, 0, s>>>(g, x, y, c.rows, c.px, c.py, c.bx, c.by, c.flags, c.r2, counts, nullptr, 0,
-                                             nullptr);
-    PMI_HIP(hipGetLastError());
-    return scan_counts(counts, c.n_picks, c.offsets, c.total, s);
+    return count_pass(c.n_picks, [&](uint32_t *counts) {
+        circle_kernel<TX, TY><<<P, BLOCK, 0, s>>>(g, x, y, c.rows, c.px, c.py, c.bx, c.by, c.flags, c.r2, counts, nullptr,
+                                                 0, nullptr);
+    }, c.offsets, c.total, s);
 }
 
 struct ShapeArgs {
@@ -339,16 +323,11 @@ template <typename TX, typename TY>
 static int shape_typed(const TX *x, const TY *y, Blocks g, const ShapeArgs &c, hipStream_t s)
 {
     const unsigned P = (unsigned)c.n_picks;
-    if (!c.members) {
-        uint32_t *counts;
-        int rc = carve(SCR_STAGE_A, [&](Arena &ar) { counts = ar.take<uint32_t>((size_t)P + 1); });
-        if (rc != PMI_OK) return rc;
-        PMI_HIP(hipMemsetAsync(counts, 0, sizeof(uint32_t) * ((size_t)P + 1), s));
-        shape_kernel<TX, TY><<<P, BLOCK, 0, s>>>(g, c.grid, x, y, c.rows, c.shape, c.bounds, c.flags, c.corner_offsets,
-                                                c.X, c.Y, c.n_corners, counts, nullptr, 0, nullptr);
-        PMI_HIP(hipGetLastError());
-        return scan_counts(counts, c.n_picks, c.offsets, c.total, s);
-    }
+    if (!c.members)
+        return count_pass(c.n_picks, [&](uint32_t *counts) {
+            shape_kernel<TX, TY><<<P, BLOCK, 0, s>>>(g, c.grid, x, y, c.rows, c.shape, c.bounds, c.flags, c.corner_offsets,
+                                                    c.X, c.Y, c.n_corners, counts, nullptr, 0, nullptr);
+        }, c.offsets, c.total, s);
     if (c.capacity == 0) return PMI_OK;
     // members in cell order, then each pick's segment sorted by row id into the caller's array
     int32_t *unsorted;
@@ -359,13 +338,11 @@ static int shape_typed(const TX *x, const TY *y, Blocks g, const ShapeArgs &c, h
                                             c.Y, c.n_corners, nullptr, c.offsets, c.capacity, unsorted);
     PMI_HIP(hipGetLastError());
     const int bits = bits_of((uint64_t)std::max(g.n - 1, 1));
-    size_t bytes = 0;
-    PMI_HIP(rocprim::segmented_radix_sort_keys(nullptr, bytes, (const uint32_t *)unsorted, (uint32_t *)c.members,
-                                               (unsigned)c.capacity, P, c.offsets, c.offsets + 1, 0u, (unsigned)bits, s));
-    void *tmp = nullptr;
-    if ((rc = scratch(SCR_STAGE_B, bytes + 64, &tmp)) != PMI_OK) return rc;
-    PMI_HIP(rocprim::segmented_radix_sort_keys(tmp, bytes, (const uint32_t *)unsorted, (uint32_t *)c.members,
-                                               (unsigned)c.capacity, P, c.offsets, c.offsets + 1, 0u, (unsigned)bits, s));
+    rc = two_pass([&](void *tmp, size_t &bytes) {
+        return rocprim::segmented_radix_sort_keys(tmp, bytes, (const uint32_t *)unsorted, (uint32_t *)c.members,
+                                                  (unsigned)c.capacity, P, c.offsets, c.offsets + 1, 0u, (unsigned)bits, s);
+    });
+    if (rc != PMI_OK) return rc;
     PMI_HIP(hipStreamSynchronize(s));
     return PMI_OK;
 }
@@ -374,6 +351,16 @@ template <typename TX, typename TY>
 static int cells_typed(const TX *x, const TY *y, int32_t n, Grid g, uint32_t *x_index, uint32_t *y_index, hipStream_t s)
 {
     PMI_LAUNCH((cells_kernel<TX, TY>), n, s, x, y, n, g, x_index, y_index);
+    PMI_HIP(hipStreamSynchronize(s));
+    return PMI_OK;
+}
+
+// a call without picks: the count pass answers offsets[0] = 0 and no members, the write pass has nothing to do
+static int no_picks(int64_t *offsets, int32_t *members, int64_t *total, hipStream_t s)
+{
+    if (members) return PMI_OK;
+    *total = 0;
+    PMI_HIP(hipMemsetAsync(offsets, 0, sizeof(int64_t), s));
     PMI_HIP(hipStreamSynchronize(s));
     return PMI_OK;
 }
@@ -395,13 +382,6 @@ static int check_grid(const char *what, const Grid &g)
 
 using namespace pmi;
 
-#define PMI_PICKS_DISPATCH(fn, ...)                                                                          \
-    (x_type == PMI_LINK_F32                                                                                  \
-         ? (y_type == PMI_LINK_F32 ? fn<float, float>((const float *)d_x, (const float *)d_y, __VA_ARGS__)   \
-                                   : fn<float, double>((const float *)d_x, (const double *)d_y, __VA_ARGS__)) \
-         : (y_type == PMI_LINK_F32 ? fn<double, float>((const double *)d_x, (const float *)d_y, __VA_ARGS__) \
-                                   : fn<double, double>((const double *)d_x, (const double *)d_y, __VA_ARGS__)))
-
 extern "C" {
 
 int pmi_picks_circle_dev(const void *d_x, int x_type, const void *d_y, int y_type, const int32_t *d_rows,
@@ -419,17 +399,11 @@ int pmi_picks_circle_dev(const void *d_x, int x_type, const void *d_y, int y_typ
         return PMI_ERR_ARG;
     }
     hipStream_t s = (hipStream_t)stream;
-    if (n_picks == 0) {
-        if (d_members) return PMI_OK;
-        *total = 0;
-        PMI_HIP(hipMemsetAsync(d_offsets, 0, sizeof(int64_t), s));
-        PMI_HIP(hipStreamSynchronize(s));
-        return PMI_OK;
-    }
-    const picks::Blocks g{d_keys, (int32_t)n, (int32_t)p, K, L};
+    if (n_picks == 0) return picks::no_picks(d_offsets, d_members, total, s);
+    const rows::Blocks g{d_keys, (int32_t)n, (int32_t)p, K, L};
     const picks::CircleArgs c{d_rows, d_pick_x, d_pick_y, d_block_x, d_block_y, d_flags, r2, n_picks, d_offsets,
                               capacity, total, d_members};
-    return PMI_PICKS_DISPATCH(picks::circle_typed, g, c, s);
+    return PMI_XY_DISPATCH(picks::circle_typed, g, c, s);
 }
 
 int pmi_picks_cells_dev(const void *d_x, int x_type, const void *d_y, int y_type, int64_t n, double x0, double y0,
@@ -445,7 +419,7 @@ int pmi_picks_cells_dev(const void *d_x, int x_type, const void *d_y, int y_type
         return PMI_ERR_ARG;
     }
     if (n == 0) return PMI_OK;
-    return PMI_PICKS_DISPATCH(picks::cells_typed, (int32_t)n, grid, d_x_index, d_y_index, (hipStream_t)stream);
+    return PMI_XY_DISPATCH(picks::cells_typed, (int32_t)n, grid, d_x_index, d_y_index, (hipStream_t)stream);
 }
 
 int pmi_picks_shape_dev(const void *d_x, int x_type, const void *d_y, int y_type, const int32_t *d_rows,
@@ -468,17 +442,11 @@ int pmi_picks_shape_dev(const void *d_x, int x_type, const void *d_y, int y_type
         return PMI_ERR_ARG;
     }
     hipStream_t s = (hipStream_t)stream;
-    if (n_picks == 0) {
-        if (d_members) return PMI_OK;
-        *total = 0;
-        PMI_HIP(hipMemsetAsync(d_offsets, 0, sizeof(int64_t), s));
-        PMI_HIP(hipStreamSynchronize(s));
-        return PMI_OK;
-    }
-    const picks::Blocks g{d_keys, (int32_t)n, (int32_t)p, CY, CX};
+    if (n_picks == 0) return picks::no_picks(d_offsets, d_members, total, s);
+    const rows::Blocks g{d_keys, (int32_t)n, (int32_t)p, CY, CX};
     const picks::ShapeArgs c{d_rows, grid, shape, d_bounds, d_flags, d_corner_offsets, d_corner_x, d_corner_y,
                              (int32_t)n_corners, n_picks, d_offsets, capacity, total, d_members};
-    return PMI_PICKS_DISPATCH(picks::shape_typed, g, c, s);
+    return PMI_XY_DISPATCH(picks::shape_typed, g, c, s);
 }
 
 }  // extern "C"

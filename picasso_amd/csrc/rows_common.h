@@ -1,7 +1,8 @@
 // rows_common.h — what the kernels over a resident localization table share: launch shape, bisection, union-find, the
-// scratch arena, the rocPRIM sorts and scan, and the argument checks of a row table.  Every post-processing source
-// includes it (aim, link, cluster, pairs, knn, frc directly; centers, kinetics, combine, areas and average through
-// rows_groups.h, the layer for tables ordered by a label column).  It pulls in rocPRIM: the fit kernels do not pay for it.
+// scratch arena, the rocPRIM sorts and scan (and the two passes of any rocPRIM call), the argument checks of a row table
+// and the dispatch over the x / y element types.  Included by aim, link, cluster, knn, frc and fiducials directly; centers, kinetics, combine, areas and average through rows_groups.h, the
+// layer for tables ordered by a label column; pairs, picks and similar through rows_blocks.h, the layer for tables in
+// block order.  It pulls in rocPRIM: the fit kernels do not pay for it.
 #pragma once
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -108,30 +109,35 @@ static int bits_of(uint64_t top)
     return bits;
 }
 
-// The rocPRIM calls; each takes its temporary from SCR_STAGE_B, which no arena of these modules is carved from.
+// The two passes of a rocPRIM call, call(void *tmp, size_t &bytes) -> hipError_t: without a temporary it only says how
+// many bytes it wants; they come from SCR_STAGE_B, which no arena of these modules is carved from.
+template <typename Call>
+static int two_pass(Call &&call)
+{
+    size_t bytes = 0;
+    PMI_HIP(call(nullptr, bytes));
+    void *tmp = nullptr;
+    const int rc = scratch(SCR_STAGE_B, bytes + 64, &tmp);
+    if (rc != PMI_OK) return rc;
+    PMI_HIP(call(tmp, bytes));
+    return PMI_OK;
+}
+
 // Stable radix sorts on the key bits [begin, begin + bits).
 template <typename K, typename V>
 static int sort_pairs(K *keys, K *keys_out, V *vals, V *vals_out, size_t n, int bits, hipStream_t stream, int begin = 0)
 {
-    size_t bytes = 0;
-    PMI_HIP(rocprim::radix_sort_pairs(nullptr, bytes, keys, keys_out, vals, vals_out, n, begin, begin + bits, stream));
-    void *tmp = nullptr;
-    const int rc = scratch(SCR_STAGE_B, bytes + 64, &tmp);
-    if (rc != PMI_OK) return rc;
-    PMI_HIP(rocprim::radix_sort_pairs(tmp, bytes, keys, keys_out, vals, vals_out, n, begin, begin + bits, stream));
-    return PMI_OK;
+    return two_pass([&](void *tmp, size_t &bytes) {
+        return rocprim::radix_sort_pairs(tmp, bytes, keys, keys_out, vals, vals_out, n, begin, begin + bits, stream);
+    });
 }
 
 template <typename K>
 static int sort_keys(K *keys, K *keys_out, size_t n, int bits, hipStream_t stream)
 {
-    size_t bytes = 0;
-    PMI_HIP(rocprim::radix_sort_keys(nullptr, bytes, keys, keys_out, n, 0, bits, stream));
-    void *tmp = nullptr;
-    const int rc = scratch(SCR_STAGE_B, bytes + 64, &tmp);
-    if (rc != PMI_OK) return rc;
-    PMI_HIP(rocprim::radix_sort_keys(tmp, bytes, keys, keys_out, n, 0, bits, stream));
-    return PMI_OK;
+    return two_pass([&](void *tmp, size_t &bytes) {
+        return rocprim::radix_sort_keys(tmp, bytes, keys, keys_out, n, 0, bits, stream);
+    });
 }
 
 // out[i] = flag[0] + ... + flag[i - 1].  F is uint32_t or const uint32_t; a template, like the sorts, so that a source
@@ -139,13 +145,9 @@ static int sort_keys(K *keys, K *keys_out, size_t n, int bits, hipStream_t strea
 template <typename F>
 static int exclusive_scan_u32(F *flag, uint32_t *out, size_t n, hipStream_t stream)
 {
-    size_t bytes = 0;
-    PMI_HIP(rocprim::exclusive_scan(nullptr, bytes, flag, out, 0u, n, rocprim::plus<uint32_t>(), stream));
-    void *tmp = nullptr;
-    const int rc = scratch(SCR_STAGE_B, bytes + 64, &tmp);
-    if (rc != PMI_OK) return rc;
-    PMI_HIP(rocprim::exclusive_scan(tmp, bytes, flag, out, 0u, n, rocprim::plus<uint32_t>(), stream));
-    return PMI_OK;
+    return two_pass([&](void *tmp, size_t &bytes) {
+        return rocprim::exclusive_scan(tmp, bytes, flag, out, 0u, n, rocprim::plus<uint32_t>(), stream);
+    });
 }
 
 // n rows, indexed with int32, in n_groups runs that `unit` names in the message (no unit: a call without runs)
@@ -170,6 +172,15 @@ static int check_xy(const char *what, int x_type, int y_type)
     }
     return PMI_OK;
 }
+
+// fn<TX, TY>((const TX *)d_x, (const TY *)d_y, ...) for the checked codes x_type / y_type of the exported function it
+// stands in
+#define PMI_XY_DISPATCH(fn, ...)                                                                             \
+    (x_type == PMI_LINK_F32                                                                                  \
+         ? (y_type == PMI_LINK_F32 ? fn<float, float>((const float *)d_x, (const float *)d_y, __VA_ARGS__)   \
+                                   : fn<float, double>((const float *)d_x, (const double *)d_y, __VA_ARGS__)) \
+         : (y_type == PMI_LINK_F32 ? fn<double, float>((const double *)d_x, (const float *)d_y, __VA_ARGS__) \
+                                   : fn<double, double>((const double *)d_x, (const double *)d_y, __VA_ARGS__)))
 
 }  // namespace rows
 }  // namespace pmi

@@ -11,7 +11,8 @@
 // are: the reference stacks x and y into one array), positions < p only (the reference's table stops filling at the
 // first row outside the K x L grid).  A point in block (ki, li) then owns three runs of positions, one per block row
 // k = ki - 1 .. ki + 1 with 0 <= k < K, blocks l = li - 1 .. li + 1 with 0 <= l < L (two bisections of the sorted keys
-// per run, as in picks.hip); they are found once and never again as the centre moves.  The gate counts the rows of the
+// per run: the clamped window of rows_blocks.h, shared with picks.hip); they are found once and never again as the
+// centre moves.  The gate, which is this source's own, counts the rows of the
 // narrower runs 0 < k < K, 0 < l < L (block row 0 and block column 0 never count; when no block qualifies the
 // reference's variable is never assigned and numba leaves it 0) and the point goes on when that count is >= gate.
 //
@@ -33,7 +34,7 @@
 #include <unordered_map>
 #include <vector>
 
-#include "rows_common.h"
+#include "rows_blocks.h"
 
 #pragma clang fp contract(off)
 
@@ -42,22 +43,13 @@ namespace similar {
 
 using namespace rows;
 
-constexpr int64_t INDEX_MAX = 0xffffffffLL;
 constexpr int64_t MAX_SHIFTS = 1 << 16;
-
-struct Blocks {
-    const uint64_t *keys;
-    int32_t p;
-    int64_t K, L;
-};
 
 struct Grid {
     const double *x, *y_base, *y_shift;
     const int64_t *bx, *by_base, *by_shift;
     int64_t n_x, n_y;
 };
-
-__device__ __forceinline__ uint64_t block_key(int64_t k, int64_t l) { return ((uint64_t)k << 32) | (uint64_t)l; }
 
 template <typename TX, typename TY, typename S>
 __global__ void gather_kernel(const TX *__restrict__ x, const TY *__restrict__ y, const int32_t *__restrict__ rows,
@@ -129,17 +121,14 @@ __global__ void shift_kernel(Blocks g, Grid grid, const S *__restrict__ xs, cons
 
     int32_t a[3] = {0, 0, 0}, b[3] = {0, 0, 0};
     int64_t gated = 0;
-    if (ki >= -1 && ki <= g.K && li >= -1 && li <= g.L) {          // else no block of the nine lies inside the grid
-        const int64_t l0 = li > 0 ? li - 1 : 0, l1 = std::min(std::min(li + 1, g.L - 1), INDEX_MAX);
+    const Window w = window(g, ki, li);
 #pragma unroll
-        for (int t = 0; t < 3; ++t) {
-            const int64_t k = ki - 1 + t;
-            if (k < 0 || k >= g.K || k > INDEX_MAX || l0 > l1) continue;
-            a[t] = lower_bound(g.keys, 0, g.p, block_key(k, l0));
-            b[t] = lower_bound(g.keys, a[t], g.p, block_key(k, l1) + 1u);
-            if (k >= 1 && l1 >= 1)                                  // the gate's blocks: 0 < k, 0 < l
-                gated += b[t] - (l0 >= 1 ? a[t] : lower_bound(g.keys, a[t], b[t], block_key(k, 1)));
-        }
+    for (int t = 0; t < 3; ++t) {
+        if (!w.row[t]) continue;
+        const int64_t k = ki - 1 + t;
+        block_run(g, k, w.l0, w.l1, &a[t], &b[t]);
+        if (k >= 1 && w.l1 >= 1)                                    // the gate's blocks: 0 < k, 0 < l
+            gated += b[t] - (w.l0 >= 1 ? a[t] : lower_bound(g.keys, a[t], b[t], block_key(k, 1)));
     }
 
     double cx = gx, cy = gy, rmsd = 0.0;
@@ -173,7 +162,6 @@ __global__ void shift_kernel(Blocks g, Grid grid, const S *__restrict__ xs, cons
 
 struct ShiftArgs {
     const int32_t *rows;
-    int32_t n;
     double r2, gate;
     int32_t max_shifts;
     double *out_x, *out_y;
@@ -188,7 +176,7 @@ static int shift_in(const TX *x, const TY *y, Blocks g, const Grid &grid, const 
     const size_t room = (size_t)std::max<int32_t>(g.p, 1);
     int rc = carve(SCR_STAGE_A, [&](Arena &ar) { xs = ar.take<S>(room); ys = ar.take<S>(room); });
     if (rc != PMI_OK) return rc;
-    if (g.p > 0) PMI_LAUNCH((gather_kernel<TX, TY, S>), g.p, s, x, y, c.rows, c.n, g.p, xs, ys);
+    if (g.p > 0) PMI_LAUNCH((gather_kernel<TX, TY, S>), g.p, s, x, y, c.rows, g.n, g.p, xs, ys);
     PMI_LAUNCH((shift_kernel<S>), grid.n_x * grid.n_y, s, g, grid, xs, ys, c.r2, c.gate, c.max_shifts, c.out_x, c.out_y,
                c.out_n, c.out_rmsd);
     PMI_HIP(hipStreamSynchronize(s));
@@ -223,13 +211,6 @@ struct Cells {
 
 using namespace pmi;
 
-#define PMI_SIMILAR_DISPATCH(fn, ...)                                                                        \
-    (x_type == PMI_LINK_F32                                                                                  \
-         ? (y_type == PMI_LINK_F32 ? fn<float, float>((const float *)d_x, (const float *)d_y, __VA_ARGS__)   \
-                                   : fn<float, double>((const float *)d_x, (const double *)d_y, __VA_ARGS__)) \
-         : (y_type == PMI_LINK_F32 ? fn<double, float>((const double *)d_x, (const float *)d_y, __VA_ARGS__) \
-                                   : fn<double, double>((const double *)d_x, (const double *)d_y, __VA_ARGS__)))
-
 extern "C" {
 
 int pmi_similar_shift_dev(const void *d_x, int x_type, const void *d_y, int y_type, const int32_t *d_rows,
@@ -242,7 +223,7 @@ int pmi_similar_shift_dev(const void *d_x, int x_type, const void *d_y, int y_ty
     const char *what = "pmi_similar_shift_dev";
     int rc = rows::check_rows(what, n);
     if (rc || (rc = rows::check_xy(what, x_type, y_type))) return rc;
-    if (p < 0 || p > n || K < 0 || L < 0 || K > similar::INDEX_MAX || L > similar::INDEX_MAX || n_x < 0 || n_y < 0 ||
+    if (p < 0 || p > n || K < 0 || L < 0 || K > rows::INDEX_MAX || L > rows::INDEX_MAX || n_x < 0 || n_y < 0 ||
         n_x > INT32_MAX - 1 || n_y > INT32_MAX - 1 || n_x * n_y > INT32_MAX - 1 || max_shifts < 0 ||
         max_shifts > similar::MAX_SHIFTS) {
         set_error("%s: %lld visible of %lld rows, grid %lld x %lld, %lld x %lld points (indexed with int32), %lld shifts "
@@ -256,10 +237,10 @@ int pmi_similar_shift_dev(const void *d_x, int x_type, const void *d_y, int y_ty
         set_error("%s: NULL argument", what);
         return PMI_ERR_ARG;
     }
-    const similar::Blocks g{d_keys, (int32_t)p, K, L};
+    const rows::Blocks g{d_keys, (int32_t)n, (int32_t)p, K, L};
     const similar::Grid grid{d_grid_x, d_grid_y_base, d_grid_y_shift, d_block_x, d_block_y_base, d_block_y_shift, n_x, n_y};
-    const similar::ShiftArgs c{d_rows, (int32_t)n, r2, gate, (int32_t)max_shifts, d_out_x, d_out_y, d_out_n, d_out_rmsd};
-    return PMI_SIMILAR_DISPATCH(similar::shift_typed, g, grid, c, (hipStream_t)stream);
+    const similar::ShiftArgs c{d_rows, r2, gate, (int32_t)max_shifts, d_out_x, d_out_y, d_out_n, d_out_rmsd};
+    return PMI_XY_DISPATCH(similar::shift_typed, g, grid, c, (hipStream_t)stream);
 }
 
 int pmi_similar_filter(const double *cand_x, const double *cand_y, int64_t n_candidates, const double *pick_x,

@@ -375,18 +375,23 @@ def _index_blocks_shape(info, size: float) -> tuple[int, int]:
     return int(np.ceil(height / size)), int(np.ceil(width / size))
 
 
-def _index_blocks(locs: pd.DataFrame, info, size: float):
+def _block_table(locs: pd.DataFrame, info, size: float, refuse_empty: bool = False):
     """The host part of get_index_blocks (postprocess.py:74-83), as the reference's own NumPy calls, and the sort on
-    the device instead of the K x L block table -> (sanity-filtered locs, backend.BlockTable).  The reference splits
-    the rows into int(N / n_threads)-row chunks and so raises on an empty table (range() with step 0) on every
-    machine; here that is the only table not computed."""
+    the device instead of the K x L block table -> (sanity-filtered locs, backend.BlockTable)."""
     locs = lib.ensure_sanity(locs, info)
     x_index = np.uint32(locs["x"].to_numpy() / size)
     y_index = np.uint32(locs["y"].to_numpy() / size)
     n_blocks_y, n_blocks_x = _index_blocks_shape(info, size)
-    if len(locs) == 0:
+    if refuse_empty and len(locs) == 0:
         raise ValueError("range() arg 3 must not be zero")
     return locs, backend.BlockTable(x_index, y_index, n_blocks_y, n_blocks_x)
+
+
+def _index_blocks(locs: pd.DataFrame, info, size: float):
+    """_block_table as get_index_blocks itself answers: the reference splits the rows into int(N / n_threads)-row
+    chunks and so raises on an empty table (range() with step 0) on every machine; here that is the only table not
+    computed."""
+    return _block_table(locs, info, size, refuse_empty=True)
 
 
 def compute_local_density(locs: pd.DataFrame, info, radius: float) -> pd.DataFrame:
@@ -897,11 +902,7 @@ def _circle_members(locs: pd.DataFrame, info: list[dict], picks: list[tuple], pi
     """-> (the sanity-filtered table, offsets, rows): the members of circular picks as positions in that table, in the
     reference's order before its sort by frame; all picks in one device call.  ``with_table`` appends the
     backend.BlockTable the call ordered the rows with."""
-    locs = lib.ensure_sanity(locs, info)
-    x_index = np.uint32(locs["x"].to_numpy() / pick_size)
-    y_index = np.uint32(locs["y"].to_numpy() / pick_size)
-    n_blocks_y, n_blocks_x = _index_blocks_shape(info, pick_size)
-    table = backend.BlockTable(x_index, y_index, n_blocks_y, n_blocks_x)
+    locs, table = _block_table(locs, info, pick_size)
     block_x = [int(x / pick_size) for x, _ in picks]
     block_y = [int(y / pick_size) for _, y in picks]
     # the reference stacks x and y into one array: a float32 beside a float64 column is float64 before any arithmetic
