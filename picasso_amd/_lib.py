@@ -215,6 +215,11 @@ def check(rc: int, what: str = ""):
         raise HipBackendError(f"{what or 'libpicasso_hip'}: status {rc}: {last_error()}")
 
 
+def call(name: str, *args):
+    """Call the exported function `name`; a status other than PMI_OK raises HipBackendError under that name."""
+    check(getattr(load(), name)(*args), name)
+
+
 def device_count() -> int:
     return int(load().pmi_device_count())
 

@@ -596,6 +596,149 @@ def localize_lq_device(d_movie_ptr, dtype, shape, box, min_ng, camera, roi=None,
     return _localize_device(call, LQ_COLUMNS, d_movie_ptr, dtype, shape, roi, frame_bounds, cap, stream, f_lo, f_hi, work)
 
 
+# ---- what the row-table wrappers below share: residence, type codes, columns, descriptor tables ----
+def _stream(device) -> int:
+    """The stream of `device` current in the calling thread, as the library takes it."""
+    import torch
+    return torch.cuda.current_stream(device).cuda_stream
+
+
+def _out(device, dtype, n, *tail, zero: bool = False):
+    """A device output of n entries (each of shape `tail`): the allocation is never empty, what comes back is its first
+    n entries.  `_dptr` hands the library the allocation even where n is 0."""
+    import torch
+    return (torch.zeros if zero else torch.empty)((max(int(n), 1),) + tail, dtype=dtype, device=device)[:int(n)]
+
+
+def _dptr(t):
+    """void* of a device tensor (None stays None).  torch gives an empty tensor the address 0; an empty slice gets the
+    start of its allocation instead, which is its own address only at offset 0: that is what `_out` returns, and an
+    empty slice further into a buffer must not come here."""
+    return None if t is None else ctypes.c_void_p(t.data_ptr() or t.untyped_storage().data_ptr())
+
+
+# The two code tables are data: (what the TypeError names, dtype -> code).  The C enums differ and stay.
+LINK_F32, LINK_F64, LINK_U32, LINK_U64 = 0, 1, 2, 3
+CENTERS_F32, CENTERS_F64, CENTERS_U32, CENTERS_I32, CENTERS_U64, CENTERS_I64 = 0, 1, 2, 3, 4, 5
+_LINK_TYPES = ("link / NeNA", {
+    np.dtype("float32"): LINK_F32, np.dtype("float64"): LINK_F64, np.dtype("uint32"): LINK_U32,
+    np.dtype("int32"): LINK_U32, np.dtype("uint64"): LINK_U64, np.dtype("int64"): LINK_U64})
+_CENTERS_TYPES = ("the cluster centers", {
+    np.dtype("float32"): CENTERS_F32, np.dtype("float64"): CENTERS_F64, np.dtype("uint32"): CENTERS_U32,
+    np.dtype("int32"): CENTERS_I32, np.dtype("uint64"): CENTERS_U64, np.dtype("int64"): CENTERS_I64})
+
+
+def _type_code(types, dtype, floating: bool = False) -> int:
+    """The code of a NumPy or torch dtype in one of the two tables; `floating` refuses the integers."""
+    what, codes = types
+    if isinstance(dtype, np.dtype):
+        dt = dtype
+    else:
+        dt = np.dtype(str(dtype)[6:] if type(dtype).__module__ == "torch" else dtype)
+    if dt not in codes or (floating and dt.kind != "f"):
+        raise TypeError(f"unsupported column dtype {dt} for {what} on the device")
+    return codes[dt]
+
+
+def link_type(dtype, floating: bool = False) -> int:
+    return _type_code(_LINK_TYPES, dtype, floating)
+
+
+def centers_type(dtype, floating: bool = False) -> int:
+    return _type_code(_CENTERS_TYPES, dtype, floating)
+
+
+def _to_device(a, dtype=None):
+    """One host column -> a device tensor (integer columns widened on the host)."""
+    import torch
+    a = np.ascontiguousarray(a if dtype is None else np.asarray(a).astype(dtype, copy=False))
+    if a.dtype == np.uint32:
+        return torch.from_numpy(a.view(np.int32)).cuda()
+    if a.dtype == np.uint64:
+        return torch.from_numpy(a.view(np.int64)).cuda()
+    return torch.from_numpy(a).cuda()
+
+
+def _index_column(a, what: str):
+    """A label, frame or offset column as the device takes it: any integer or bool column, widened to int64."""
+    a = np.asarray(a)
+    if a.dtype.kind not in "iub":
+        raise TypeError(f"{what} must be an integer column, not {a.dtype}")
+    return a.astype(np.int64, copy=False)
+
+
+def _centers_column(a, what: str) -> np.ndarray:
+    """A table column as the device takes it: bool and the narrow integers widened (to a type pandas would convert
+    to float64 all the same), float16 refused."""
+    a = np.asarray(a)
+    if a.dtype.kind == "b" or (a.dtype.kind in "iu" and a.dtype.itemsize < 4):
+        a = a.astype(np.int32 if a.dtype.kind != "u" else np.uint32)
+    if a.ndim != 1:
+        raise ValueError(f"{what} must be a column, not an array of shape {a.shape}")
+    centers_type(a.dtype)
+    return a
+
+
+def _float_column(a):
+    """A float32 / float64 column, host or device -> (device tensor, LINK type code)."""
+    import torch
+    if isinstance(a, torch.Tensor):
+        if a.dtype not in (torch.float32, torch.float64) or a.dim() != 1 or not a.is_cuda:
+            raise TypeError("a device column must be a 1-D float32 or float64 tensor on the GPU")
+        return a.contiguous(), link_type(a.dtype)
+    a = np.asarray(a)
+    return _to_device(a), link_type(a.dtype, True)
+
+
+def _check_points(X: np.ndarray) -> np.ndarray:
+    if X.ndim != 2 or X.shape[1] not in (2, 3):
+        raise ValueError(f"points must have shape (n, 2) or (n, 3), not {X.shape}")
+    return X
+
+
+def _check_rows(n: int, message: str, *columns) -> None:
+    """The one length check: every column has n entries."""
+    if any(len(c) != n for c in columns):
+        raise ValueError(message)
+
+
+_PER_ROW = "every column must have one entry per row of the table"
+
+
+class _Uploads(dict):
+    """One upload per host column of a table of n rows, however many calls read it."""
+
+    def __init__(self, n: int):
+        super().__init__()
+        self.n = int(n)
+
+    def column(self, a):
+        # two views of one column are one upload; a shorter view of it is another column, and is refused below
+        key = (a.__array_interface__["data"][0], a.shape, a.strides, a.dtype.str)
+        if key not in self:
+            _check_rows(self.n, _PER_ROW, a)
+            self[key] = (a, _to_device(a))
+        return self[key][1]
+
+
+class _Table:
+    """The descriptor table of one statistics call.  `rows` holds one tuple per descriptor in the field order of the
+    ctypes structure `struct`: a device tensor (or None) for a pointer field, a code for an integer one.  The table
+    references every tensor it points to, so the caller keeps the table until the call has returned and reads the
+    outputs from `rows`."""
+
+    def __init__(self, struct, rows):
+        self.rows = rows
+        self.array = (struct * max(len(rows), 1))(*[
+            struct(*[f if f is None or type(f) is int else f.data_ptr() for f in row]) for row in rows])
+        self.ptr, self.count = ctypes.cast(self.array, ctypes.c_void_p), len(rows)
+
+    @classmethod
+    def chunks(cls, struct, rows, limit: int):
+        """One table per `limit` rows, for a call that takes no more descriptors at a time."""
+        return [cls(struct, rows[lo:lo + limit]) for lo in range(0, len(rows), limit)]
+
+
 # ---- AIM undrift: intersection counts (csrc/aim.hip, picasso/aim.py:517-773) ----
 AIM_XY_F32, AIM_XY_F64, AIM_Z_F32, AIM_Z_F64 = 0, 1, 2, 3
 
@@ -608,16 +751,10 @@ def aim_partition(d_frame, seg_len: int, n_frames: int):
     n_seg = -(-int(n_frames) // int(seg_len)) if n_frames > 0 else 0
     rows = torch.empty(max(n, 1), dtype=torch.int32, device=d_frame.device)
     offsets = np.zeros(n_seg + 1, np.int64)
-    stream = torch.cuda.current_stream(d_frame.device).cuda_stream
     with _lib.lock():
-        _lib.check(_lib.load().pmi_aim_partition_dev(ctypes.c_void_p(d_frame.data_ptr()), n, int(seg_len), int(n_frames),
-                                                     ctypes.c_void_p(rows.data_ptr()), _lib.ptr(offsets),
-                                                     ctypes.c_void_p(stream)), "pmi_aim_partition_dev")
+        _lib.call("pmi_aim_partition_dev", ctypes.c_void_p(d_frame.data_ptr()), n, int(seg_len), int(n_frames),
+                  ctypes.c_void_p(rows.data_ptr()), _lib.ptr(offsets), ctypes.c_void_p(_stream(d_frame.device)))
     return rows, offsets
-
-
-def _dptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
 class AimTable:
@@ -629,27 +766,25 @@ class AimTable:
         self.mode, self.x, self.y, self.z = int(mode), x, y, z
         self.shifts = np.ascontiguousarray(shifts, np.int32 if mode in (AIM_XY_F32, AIM_XY_F64) else np.float64)
         self.n_shifts = int(self.shifts.size)
-        self.device = x.device
-        self.stream = torch.cuda.current_stream(self.device).cuda_stream
+        self.device, self.stream = x.device, _stream(x.device)
         self.out = torch.zeros(self.n_shifts + 1, dtype=torch.int32, device=self.device)
         self._h = ctypes.c_void_p()
         with _lib.lock():
-            _lib.check(_lib.load().pmi_aim_table_create_dev(
-                self.mode, _dptr(x), _dptr(y), _dptr(z), _dptr(ref_rows), int(n_ref), float(intersect_d),
-                float(width_units), float(height_units), _lib.ptr(self.shifts), self.n_shifts, ctypes.byref(self._h),
-                ctypes.c_void_p(self.stream)), "pmi_aim_table_create_dev")
+            _lib.call("pmi_aim_table_create_dev", self.mode, _dptr(x), _dptr(y), _dptr(z), _dptr(ref_rows), int(n_ref),
+                      float(intersect_d), float(width_units), float(height_units), _lib.ptr(self.shifts), self.n_shifts,
+                      ctypes.byref(self._h), ctypes.c_void_p(self.stream))
 
     def info(self):
         dense, entries = ctypes.c_int(0), ctypes.c_int64(0)
-        _lib.check(_lib.load().pmi_aim_table_info(self._h, ctypes.byref(dense), ctypes.byref(entries)), "pmi_aim_table_info")
+        _lib.call("pmi_aim_table_info", self._h, ctypes.byref(dense), ctypes.byref(entries))
         return ("dense" if dense.value else "sorted"), int(entries.value)
 
     def count(self, rows, rel_x=0.0, rel_y=0.0, rel_z=0.0) -> np.ndarray:
         """int64 roi_cc of the target rows `rows` (an int32 device tensor) shifted by rel; one D2H of n_shifts + 1 ints."""
         with _lib.lock():
-            _lib.check(_lib.load().pmi_aim_count_dev(
-                self._h, _dptr(self.x), _dptr(self.y), _dptr(self.z), _dptr(rows), int(rows.numel()), float(rel_x),
-                float(rel_y), float(rel_z), _dptr(self.out), ctypes.c_void_p(self.stream)), "pmi_aim_count_dev")
+            _lib.call("pmi_aim_count_dev", self._h, _dptr(self.x), _dptr(self.y), _dptr(self.z), _dptr(rows),
+                      int(rows.numel()), float(rel_x), float(rel_y), float(rel_z), _dptr(self.out),
+                      ctypes.c_void_p(self.stream))
             h = self.out.cpu().numpy()
         if h[-1]:
             raise _lib.HipBackendError(f"pmi_aim_count_dev: status {int(h[-1])} (target hash overflow)")
@@ -669,7 +804,7 @@ class AimTable:
 
 def aim_set_dense_limit(entries: int) -> None:
     """Spans of more target-counter entries than this take the sorted table form (default 2**28)."""
-    _lib.check(_lib.load().pmi_aim_set_dense_limit(int(entries)), "pmi_aim_set_dense_limit")
+    _lib.call("pmi_aim_set_dense_limit", int(entries))
 
 
 def aim_roi_cc_arrays(mode, ref, target, rel, intersect_d, width_units, height_units, shifts) -> np.ndarray:
@@ -688,19 +823,14 @@ def aim_roi_cc_arrays(mode, ref, target, rel, intersect_d, width_units, height_u
     out = np.zeros(sh.size, np.int64)
     rel = tuple(rel) + (0.0,) * (3 - len(rel))
     with _lib.lock():
-        _lib.check(_lib.load().pmi_aim_roi_cc(int(mode), _lib.ptr(r[0]), _lib.ptr(r[1]), _lib.ptr(r[2]), len(r[0]),
-                                              _lib.ptr(t[0]), _lib.ptr(t[1]), _lib.ptr(t[2]), len(t[0]),
-                                              float(rel[0]), float(rel[1]), float(rel[2]), float(intersect_d),
-                                              float(width_units), float(height_units), _lib.ptr(sh), int(sh.size),
-                                              _lib.ptr(out)), "pmi_aim_roi_cc")
+        _lib.call("pmi_aim_roi_cc", int(mode), _lib.ptr(r[0]), _lib.ptr(r[1]), _lib.ptr(r[2]), len(r[0]), _lib.ptr(t[0]),
+                  _lib.ptr(t[1]), _lib.ptr(t[2]), len(t[0]), float(rel[0]), float(rel[1]), float(rel[2]),
+                  float(intersect_d), float(width_units), float(height_units), _lib.ptr(sh), int(sh.size), _lib.ptr(out))
     return out
 
 
 # ---- link and NeNA (csrc/link.hip, picasso/postprocess.py:2441-2661, :1212-1272) ----
-LINK_F32, LINK_F64, LINK_U32, LINK_U64 = 0, 1, 2, 3
 LINK_SUM, LINK_WSUM, LINK_XWSUM = 0, 1, 2
-_LINK_TYPES = {np.dtype("float32"): LINK_F32, np.dtype("float64"): LINK_F64, np.dtype("uint32"): LINK_U32,
-               np.dtype("int32"): LINK_U32, np.dtype("uint64"): LINK_U64, np.dtype("int64"): LINK_U64}
 
 
 class _LinkColumn(ctypes.Structure):
@@ -708,80 +838,49 @@ class _LinkColumn(ctypes.Structure):
                 ("op", ctypes.c_int32), ("type", ctypes.c_int32), ("w_type", ctypes.c_int32)]
 
 
-def link_type(dtype, floating: bool = False) -> int:
-    dt = np.dtype(dtype)
-    if dt not in _LINK_TYPES or (floating and dt.kind != "f"):
-        raise TypeError(f"unsupported column dtype {dt} for link / NeNA on the device")
-    return _LINK_TYPES[dt]
-
-
-def _to_device(a, dtype=None):
-    """One host column -> a device tensor (integer columns widened on the host)."""
-    import torch
-    a = np.ascontiguousarray(a if dtype is None else np.asarray(a).astype(dtype, copy=False))
-    if a.dtype == np.uint32:
-        return torch.from_numpy(a.view(np.int32)).cuda()
-    if a.dtype == np.uint64:
-        return torch.from_numpy(a.view(np.int64)).cuda()
-    return torch.from_numpy(a).cuda()
-
-
-def _index_column(a, what: str):
-    a = np.asarray(a)
-    if a.dtype.kind not in "iub":
-        raise TypeError(f"{what} must be an integer column, not {a.dtype}")
-    return a.astype(np.int64, copy=False)
-
-
 class LinkTable:
     """frame, x, y, group of a table sorted by frame, sent to the device once (frame / group widened to int64 on
     the host; x / y stay float32 or float64, each on its own)."""
 
     def __init__(self, frame, x, y, group):
-        import torch
         _lib.require_gpu()
         x, y = np.asarray(x), np.asarray(y)
         self.n = int(len(x))
-        if not (len(frame) == len(y) == len(group) == self.n):
-            raise ValueError("frame, x, y and group must have one length")
+        _check_rows(self.n, "frame, x, y and group must have one length", frame, y, group)
         self.x_type, self.y_type = link_type(x.dtype, True), link_type(y.dtype, True)
         self.frame = _to_device(_index_column(frame, "frame"))
         self.group = _to_device(_index_column(group, "group"))
         self.x, self.y = _to_device(x), _to_device(y)
-        self.device = self.x.device
-        self.stream = torch.cuda.current_stream(self.device).cuda_stream
+        self.device, self.stream = self.x.device, _stream(self.x.device)
 
     def frame_index(self, k: int):
         """(lo, hi) int32 device tensors of pmi_link_frame_index_dev."""
         import torch
-        lo = torch.empty(max(self.n, 1), dtype=torch.int32, device=self.device)
-        hi = torch.empty(max(self.n, 1), dtype=torch.int32, device=self.device)
+        lo, hi = _out(self.device, torch.int32, self.n), _out(self.device, torch.int32, self.n)
         with _lib.lock():
-            _lib.check(_lib.load().pmi_link_frame_index_dev(_dptr(self.frame), self.n, int(k), _dptr(lo), _dptr(hi),
-                                                            ctypes.c_void_p(self.stream)), "pmi_link_frame_index_dev")
-        return lo[:self.n], hi[:self.n]
+            _lib.call("pmi_link_frame_index_dev", _dptr(self.frame), self.n, int(k), _dptr(lo), _dptr(hi),
+                      ctypes.c_void_p(self.stream))
+        return lo, hi
 
     def link_groups(self, r2: float, k: int):
         """-> (int32 device tensor link_group, number of groups)."""
         import torch
-        out = torch.empty(max(self.n, 1), dtype=torch.int32, device=self.device)
+        out = _out(self.device, torch.int32, self.n)
         n_groups = ctypes.c_int64(0)
         with _lib.lock():
-            _lib.check(_lib.load().pmi_link_groups_dev(
-                _dptr(self.frame), _dptr(self.x), self.x_type, _dptr(self.y), self.y_type, _dptr(self.group), self.n,
-                float(r2), int(k), _dptr(out), ctypes.byref(n_groups), ctypes.c_void_p(self.stream)),
-                "pmi_link_groups_dev")
-        return out[:self.n], int(n_groups.value)
+            _lib.call("pmi_link_groups_dev", _dptr(self.frame), _dptr(self.x), self.x_type, _dptr(self.y), self.y_type,
+                      _dptr(self.group), self.n, float(r2), int(k), _dptr(out), ctypes.byref(n_groups),
+                      ctypes.c_void_p(self.stream))
+        return out, int(n_groups.value)
 
     def nena_hist(self, d_max: float, bin_size: float, n_bins: int) -> np.ndarray:
         """int64 counts of the next-frame neighbour distance histogram."""
         import torch
         hist = torch.zeros(int(n_bins), dtype=torch.int64, device=self.device)
         with _lib.lock():
-            _lib.check(_lib.load().pmi_nena_hist_dev(
-                _dptr(self.frame), _dptr(self.x), self.x_type, _dptr(self.y), self.y_type, _dptr(self.group), self.n,
-                float(d_max), float(bin_size), int(n_bins), _dptr(hist), ctypes.c_void_p(self.stream)),
-                "pmi_nena_hist_dev")
+            _lib.call("pmi_nena_hist_dev", _dptr(self.frame), _dptr(self.x), self.x_type, _dptr(self.y), self.y_type,
+                      _dptr(self.group), self.n, float(d_max), float(bin_size), int(n_bins), _dptr(hist),
+                      ctypes.c_void_p(self.stream))
             return hist.cpu().numpy()
 
 
@@ -795,17 +894,8 @@ def link_combine(link_group, n_groups: int, frame, columns):
     d_lg = link_group if isinstance(link_group, torch.Tensor) else _to_device(np.asarray(link_group, np.int32))
     dev = d_lg.device
     d_frame = None if frame is None else _to_device(_index_column(frame, "frame"))
-    cache, keep, outs = {}, [], []
-
-    def dev_col(a):
-        if a is None:
-            return None
-        if id(a) not in cache:
-            cache[id(a)] = _to_device(a)
-        return cache[id(a)]
-
-    desc = (_LinkColumn * max(len(columns), 1))()
-    for i, (op, data, weight) in enumerate(columns):
+    uploads, rows, out_dts = _Uploads(n), [], []
+    for op, data, weight in columns:
         ta = link_type(data.dtype, op == LINK_XWSUM) if data is not None else 0
         tw = link_type(weight.dtype, True) if weight is not None else 0
         if op == LINK_SUM:
@@ -814,25 +904,19 @@ def link_combine(link_group, n_groups: int, frame, columns):
             out_dt = weight.dtype
         else:
             out_dt = np.promote_types(data.dtype, weight.dtype)
-        out = _to_device(np.zeros(max(G, 1), out_dt))
-        d, w = dev_col(data), dev_col(weight)
-        keep += [d, w]
-        outs.append((out, np.dtype(out_dt)))
-        desc[i] = _LinkColumn(d.data_ptr() if d is not None else None, w.data_ptr() if w is not None else None,
-                              out.data_ptr(), int(op), ta, tw)
-    count = torch.zeros(max(G, 1), dtype=torch.int32, device=dev)
-    first = torch.zeros(max(G, 1), dtype=torch.int64, device=dev)
-    last = torch.zeros(max(G, 1), dtype=torch.int64, device=dev)
-    last_row = torch.zeros(max(G, 1), dtype=torch.int32, device=dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
+        out_dts.append(np.dtype(out_dt))
+        rows.append((None if data is None else uploads.column(data), None if weight is None else uploads.column(weight),
+                     _to_device(np.zeros(max(G, 1), out_dt)), int(op), ta, tw))
+    table = _Table(_LinkColumn, rows)
+    count = _out(dev, torch.int32, G, zero=True)
+    first, last = _out(dev, torch.int64, G, zero=True), _out(dev, torch.int64, G, zero=True)
+    last_row = _out(dev, torch.int32, G, zero=True)
     with _lib.lock():
-        _lib.check(_lib.load().pmi_link_combine_dev(
-            _dptr(d_lg), n, G, _dptr(d_frame), ctypes.cast(desc, ctypes.c_void_p), len(columns), _dptr(count),
-            _dptr(first) if d_frame is not None else None, _dptr(last) if d_frame is not None else None,
-            _dptr(last_row), ctypes.c_void_p(stream)), "pmi_link_combine_dev")
-        sums = [o.cpu().numpy().view(dt)[:G] for o, dt in outs]
-        res = (count.cpu().numpy().view(np.uint32)[:G], first.cpu().numpy()[:G], last.cpu().numpy()[:G],
-               last_row.cpu().numpy()[:G])
+        _lib.call("pmi_link_combine_dev", _dptr(d_lg), n, G, _dptr(d_frame), table.ptr, table.count, _dptr(count),
+                  _dptr(first) if d_frame is not None else None, _dptr(last) if d_frame is not None else None,
+                  _dptr(last_row), ctypes.c_void_p(_stream(dev)))
+        sums = [row[2].cpu().numpy().view(dt)[:G] for row, dt in zip(table.rows, out_dts)]
+        res = (count.cpu().numpy().view(np.uint32), first.cpu().numpy(), last.cpu().numpy(), last_row.cpu().numpy())
     return res + (sums,)
 
 
@@ -844,9 +928,7 @@ class ClusterPoints:
     def __init__(self, X):
         import torch
         _lib.require_gpu()
-        X = np.asarray(X)
-        if X.ndim != 2 or X.shape[1] not in (2, 3):
-            raise ValueError(f"points must have shape (n, 2) or (n, 3), not {X.shape}")
+        X = _check_points(np.asarray(X))
         self.n, self.dims = int(X.shape[0]), int(X.shape[1])
         cols = np.ascontiguousarray(X.T, np.float64)
         if self.n:
@@ -854,12 +936,11 @@ class ClusterPoints:
         else:
             self.lo = self.hi = np.zeros(self.dims)
         self.X = torch.from_numpy(cols).cuda()
-        self.device = self.X.device
-        self.stream = torch.cuda.current_stream(self.device).cuda_stream
+        self.device, self.stream = self.X.device, _stream(self.X.device)
 
-    def _out(self):
+    def _row_out(self):
         import torch
-        return torch.empty(max(self.n, 1), dtype=torch.int32, device=self.device)
+        return _out(self.device, torch.int32, self.n)
 
     def _head(self, radius):
         r = float(radius)
@@ -867,33 +948,30 @@ class ClusterPoints:
 
     def counts(self, radius) -> np.ndarray:
         """int32 neighbour count of every row (itself included)."""
-        out = self._out()
+        out = self._row_out()
         with _lib.lock():
-            _lib.check(_lib.load().pmi_cluster_counts_dev(*self._head(radius), _dptr(out), ctypes.c_void_p(self.stream)),
-                       "pmi_cluster_counts_dev")
-            return out[:self.n].cpu().numpy()
+            _lib.call("pmi_cluster_counts_dev", *self._head(radius), _dptr(out), ctypes.c_void_p(self.stream))
+            return out.cpu().numpy()
 
     def smlm(self, radius, min_locs: int, frame=None, fa_lo=0.0, fa_hi=0.0, fa_edges=None) -> np.ndarray:
         """int32 labels of the SMLM clusterer; `frame` (any integer column) adds the frame analysis."""
-        out = self._out()
+        out = self._row_out()
         d_frame = None if frame is None else _to_device(_index_column(frame, "frame"))
         edges = None if fa_edges is None else np.ascontiguousarray(fa_edges, np.float64)
         if d_frame is not None and (edges is None or edges.size != 21 or len(frame) != self.n):
             raise ValueError("frame analysis needs one frame per row and 21 bin edges")
         with _lib.lock():
-            _lib.check(_lib.load().pmi_cluster_smlm_dev(
-                *self._head(radius), int(min_locs), _dptr(d_frame), float(fa_lo), float(fa_hi), _lib.ptr(edges),
-                _dptr(out), ctypes.c_void_p(self.stream)), "pmi_cluster_smlm_dev")
-            return out[:self.n].cpu().numpy()
+            _lib.call("pmi_cluster_smlm_dev", *self._head(radius), int(min_locs), _dptr(d_frame), float(fa_lo),
+                      float(fa_hi), _lib.ptr(edges), _dptr(out), ctypes.c_void_p(self.stream))
+            return out.cpu().numpy()
 
     def dbscan(self, radius, min_samples: int, min_locs: int) -> np.ndarray:
         """int32 DBSCAN labels, clusters of fewer than `min_locs` rows already -1."""
-        out = self._out()
+        out = self._row_out()
         with _lib.lock():
-            _lib.check(_lib.load().pmi_cluster_dbscan_dev(
-                *self._head(radius), int(min_samples), int(min_locs), _dptr(out), ctypes.c_void_p(self.stream)),
-                "pmi_cluster_dbscan_dev")
-            return out[:self.n].cpu().numpy()
+            _lib.call("pmi_cluster_dbscan_dev", *self._head(radius), int(min_samples), int(min_locs), _dptr(out),
+                      ctypes.c_void_p(self.stream))
+            return out.cpu().numpy()
 
 
 def cluster_frame_analysis(ids, frame, n_ids: int, fa_lo: float, fa_hi: float, fa_edges) -> np.ndarray:
@@ -905,13 +983,11 @@ def cluster_frame_analysis(ids, frame, n_ids: int, fa_lo: float, fa_hi: float, f
     edges = np.ascontiguousarray(fa_edges, np.float64)
     if edges.size != 21 or len(ids) != len(frame):
         raise ValueError("frame analysis needs one frame per row and 21 bin edges")
-    passed = torch.ones(max(int(n_ids), 1), dtype=torch.int32, device=d_ids.device)
-    stream = torch.cuda.current_stream(d_ids.device).cuda_stream
+    passed = _out(d_ids.device, torch.int32, n_ids).fill_(1)
     with _lib.lock():
-        _lib.check(_lib.load().pmi_cluster_frame_analysis_dev(
-            _dptr(d_ids), _dptr(d_frame), len(ids), int(n_ids), float(fa_lo), float(fa_hi), _lib.ptr(edges),
-            _dptr(passed), ctypes.c_void_p(stream)), "pmi_cluster_frame_analysis_dev")
-        return passed[:int(n_ids)].cpu().numpy()
+        _lib.call("pmi_cluster_frame_analysis_dev", _dptr(d_ids), _dptr(d_frame), len(ids), int(n_ids), float(fa_lo),
+                  float(fa_hi), _lib.ptr(edges), _dptr(passed), ctypes.c_void_p(_stream(d_ids.device)))
+        return passed.cpu().numpy()
 
 
 # ---- local density and the distance histogram (csrc/pairs.hip, picasso/postprocess.py:37-204, :960-999, :1543-1579) ----
@@ -921,7 +997,6 @@ class BlockTable:
     position at which the reference's block table stops filling (n when every row lies inside the K x L grid)."""
 
     def __init__(self, x_index, y_index, K: int, L: int):
-        import torch
         _lib.require_gpu()
         x_index, y_index = np.asarray(x_index), np.asarray(y_index)
         if x_index.dtype != np.uint32 or y_index.dtype != np.uint32 or x_index.shape != y_index.shape or x_index.ndim != 1:
@@ -939,68 +1014,52 @@ class BlockTable:
 
     def _order(self, d_xi, d_yi):
         import torch
-        self.device = d_xi.device
-        self.stream = torch.cuda.current_stream(self.device).cuda_stream
-        self.rows = torch.empty(max(self.n, 1), dtype=torch.int32, device=self.device)
-        self.keys = torch.empty(max(self.n, 1), dtype=torch.int64, device=self.device)
+        self.device, self.stream = d_xi.device, _stream(d_xi.device)
+        self.rows = _out(self.device, torch.int32, self.n)
+        self.keys = _out(self.device, torch.int64, self.n)
         p = ctypes.c_int64(0)
         with _lib.lock():
-            _lib.check(_lib.load().pmi_pairs_order_dev(_dptr(d_xi), _dptr(d_yi), self.n, self.K, self.L, _dptr(self.rows),
-                                                       _dptr(self.keys), ctypes.byref(p), ctypes.c_void_p(self.stream)),
-                       "pmi_pairs_order_dev")
+            _lib.call("pmi_pairs_order_dev", _dptr(d_xi), _dptr(d_yi), self.n, self.K, self.L, _dptr(self.rows),
+                      _dptr(self.keys), ctypes.byref(p), ctypes.c_void_p(self.stream))
         self.p = int(p.value)
 
     def order(self) -> np.ndarray:
         """The int64 permutation into block order."""
-        return self.rows[:self.n].cpu().numpy().astype(np.int64)
+        return self.rows.cpu().numpy().astype(np.int64)
 
     def _columns(self, x, y):
         """x / y of the table's rows, host arrays or device tensors -> (d_x, x type code, d_y, y type code)."""
-        d_x, tx = _pick_column(x)
-        d_y, ty = _pick_column(y)
-        if len(d_x) != self.n or len(d_y) != self.n:
-            raise ValueError("x and y must have one entry per row of the table")
+        d_x, tx = _float_column(x)
+        d_y, ty = _float_column(y)
+        _check_rows(self.n, "x and y must have one entry per row of the table", d_x, d_y)
         return d_x, tx, d_y, ty
 
     def density(self, x, y, r2: float) -> np.ndarray:
         """uint32 neighbour count of every row, in block order; x / y in the caller's row order."""
         import torch
         d_x, tx, d_y, ty = self._columns(x, y)
-        out = torch.zeros(max(self.n, 1), dtype=torch.int32, device=self.device)
+        out = _out(self.device, torch.int32, self.n, zero=True)
         with _lib.lock():
-            _lib.check(_lib.load().pmi_pairs_density_dev(
-                _dptr(d_x), tx, _dptr(d_y), ty, _dptr(self.rows), _dptr(self.keys), self.n, self.p, self.K, self.L,
-                float(r2), _dptr(out), ctypes.c_void_p(self.stream)), "pmi_pairs_density_dev")
-            return out[:self.n].cpu().numpy().view(np.uint32)
+            _lib.call("pmi_pairs_density_dev", _dptr(d_x), tx, _dptr(d_y), ty, _dptr(self.rows), _dptr(self.keys), self.n,
+                      self.p, self.K, self.L, float(r2), _dptr(out), ctypes.c_void_p(self.stream))
+            return out.cpu().numpy().view(np.uint32)
 
     def distance_hist(self, x, y, r_max: float, r2: float, bin_size: float, n_bins: int) -> np.ndarray:
         """uint64 counts of the distance histogram."""
         import torch
         d_x, tx, d_y, ty = self._columns(x, y)
-        hist = torch.zeros(max(int(n_bins), 1), dtype=torch.int64, device=self.device)
+        hist = _out(self.device, torch.int64, n_bins, zero=True)
         with _lib.lock():
-            _lib.check(_lib.load().pmi_pairs_distance_hist_dev(
-                _dptr(d_x), tx, _dptr(d_y), ty, _dptr(self.rows), _dptr(self.keys), self.n, self.p, self.K, self.L,
-                float(r_max), float(r2), float(bin_size), int(n_bins), _dptr(hist), ctypes.c_void_p(self.stream)),
-                "pmi_pairs_distance_hist_dev")
-            return hist[:int(n_bins)].cpu().numpy().view(np.uint64)
+            _lib.call("pmi_pairs_distance_hist_dev", _dptr(d_x), tx, _dptr(d_y), ty, _dptr(self.rows), _dptr(self.keys),
+                      self.n, self.p, self.K, self.L, float(r_max), float(r2), float(bin_size), int(n_bins), _dptr(hist),
+                      ctypes.c_void_p(self.stream))
+            return hist.cpu().numpy().view(np.uint64)
 
 
 # ---- picked localizations (csrc/picks.hip, picasso/postprocess.py:207-473, picasso/lib.py:1884-2004) ----
 PICK_SQUARE, PICK_RECTANGLE, PICK_POLYGON = 0, 1, 2
 PICK_MAX_CELLS = 1 << 14          # cells per axis of the grid the box shapes are binned on
 _PICK_FAR = 8e307                 # bounds are clipped here so that the grid's extent stays finite
-
-
-def _pick_column(a):
-    """A float32 / float64 column, host or device -> (device tensor, type code)."""
-    import torch
-    if isinstance(a, torch.Tensor):
-        if a.dtype not in (torch.float32, torch.float64) or a.dim() != 1 or not a.is_cuda:
-            raise TypeError("a device column must be a 1-D float32 or float64 tensor on the GPU")
-        return a.contiguous(), LINK_F32 if a.dtype == torch.float32 else LINK_F64
-    a = np.asarray(a)
-    return _to_device(a), link_type(a.dtype, True)
 
 
 def _grid_blocks(a):
@@ -1012,16 +1071,17 @@ def _grid_blocks(a):
     return np.clip(_index_column(a, "block indices"), -2, 1 << 33)
 
 
-def _picks_csr(call, n_picks: int, device):
-    """The two passes of a pick call: count (offsets and the total, the one copy to the host), then write."""
+def _picks_csr(name: str, head, n_picks: int, device, stream):
+    """The two passes of the pick call `name`, whose arguments begin with `head` and end with the CSR outputs and the
+    stream: count (offsets and the total, the one copy to the host), then write."""
     import torch
     offsets = torch.zeros(n_picks + 1, dtype=torch.int64, device=device)
     total = ctypes.c_int64(0)
-    _lib.check(call(_dptr(offsets), None, 0, ctypes.byref(total)), "pmi_picks (count)")
-    rows = torch.empty(max(int(total.value), 1), dtype=torch.int32, device=device)
+    _lib.call(name, *head, _dptr(offsets), None, 0, ctypes.byref(total), stream)
+    rows = _out(device, torch.int32, total.value)
     if total.value:
-        _lib.check(call(_dptr(offsets), _dptr(rows), int(total.value), None), "pmi_picks (write)")
-    return offsets.cpu().numpy(), rows[:int(total.value)].cpu().numpy().astype(np.int64)
+        _lib.call(name, *head, _dptr(offsets), _dptr(rows), int(total.value), None, stream)
+    return offsets.cpu().numpy(), rows.cpu().numpy().astype(np.int64)
 
 
 def picks_circle(table: "BlockTable", x, y, pick_x, pick_y, block_x, block_y, flags, r2: float):
@@ -1038,12 +1098,10 @@ def picks_circle(table: "BlockTable", x, y, pick_x, pick_y, block_x, block_y, fl
     d_px, d_py = _to_device(pick_x, np.float64), _to_device(pick_y, np.float64)
     d_bx, d_by = _to_device(_grid_blocks(block_x)), _to_device(_grid_blocks(block_y))
     d_f = _to_device(flags, np.uint8)
-    L = _lib.load()
+    head = (_dptr(d_x), tx, _dptr(d_y), ty, _dptr(table.rows), _dptr(table.keys), table.n, table.p, table.K, table.L,
+            _dptr(d_px), _dptr(d_py), _dptr(d_bx), _dptr(d_by), _dptr(d_f), P, float(r2))
     with _lib.lock():
-        return _picks_csr(lambda off, rows, cap, total: L.pmi_picks_circle_dev(
-            _dptr(d_x), tx, _dptr(d_y), ty, _dptr(table.rows), _dptr(table.keys), table.n, table.p, table.K, table.L,
-            _dptr(d_px), _dptr(d_py), _dptr(d_bx), _dptr(d_by), _dptr(d_f), P, float(r2), off, rows, cap, total,
-            ctypes.c_void_p(table.stream)), P, table.device)
+        return _picks_csr("pmi_picks_circle_dev", head, P, table.device, ctypes.c_void_p(table.stream))
 
 
 def _pick_grid(bounds, flags, tx: int, ty: int):
@@ -1076,16 +1134,14 @@ def _pick_grid(bounds, flags, tx: int, ty: int):
 def _picks_shape(shape: int, x, y, bounds, flags, corner_offsets=None, corner_x=None, corner_y=None):
     import torch
     _lib.require_gpu()
-    d_x, tx = _pick_column(x)
-    d_y, ty = _pick_column(y)
+    d_x, tx = _float_column(x)
+    d_y, ty = _float_column(y)
     n = len(d_x)
-    if len(d_y) != n:
-        raise ValueError("x and y must have one length")
+    _check_rows(n, "x and y must have one length", d_y)
     bounds = np.ascontiguousarray(bounds, np.float64).reshape(-1, 4)
     flags = np.ascontiguousarray(flags, np.uint8)
     P = len(bounds)
-    if len(flags) != P:
-        raise ValueError("one flag byte per pick")
+    _check_rows(P, "one flag byte per pick", flags)
     if P == 0:
         return np.zeros(1, np.int64), np.zeros(0, np.int64)
     n_corners = 0
@@ -1104,19 +1160,16 @@ def _picks_shape(shape: int, x, y, bounds, flags, corner_offsets=None, corner_x=
     x0, y0, x1, y1, cell, CX, CY = _pick_grid(bounds, flags, tx, ty)
     d_b, d_f = _to_device(bounds.reshape(-1)), _to_device(flags)
     device = d_x.device
-    stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-    d_xi = torch.empty(max(n, 1), dtype=torch.int32, device=device)
-    d_yi = torch.empty(max(n, 1), dtype=torch.int32, device=device)
-    L = _lib.load()
+    stream = ctypes.c_void_p(_stream(device))
+    d_xi, d_yi = _out(device, torch.int32, n), _out(device, torch.int32, n)
     with _lib.lock():
-        _lib.check(L.pmi_picks_cells_dev(_dptr(d_x), tx, _dptr(d_y), ty, n, x0, y0, x1, y1, cell, CX, CY, _dptr(d_xi),
-                                         _dptr(d_yi), stream), "pmi_picks_cells_dev")
-    table = BlockTable.from_device(d_xi[:n], d_yi[:n], CY, CX)
+        _lib.call("pmi_picks_cells_dev", _dptr(d_x), tx, _dptr(d_y), ty, n, x0, y0, x1, y1, cell, CX, CY, _dptr(d_xi),
+                  _dptr(d_yi), stream)
+    table = BlockTable.from_device(d_xi, d_yi, CY, CX)
+    head = (_dptr(d_x), tx, _dptr(d_y), ty, _dptr(table.rows), _dptr(table.keys), n, table.p, x0, y0, x1, y1, cell, CX,
+            CY, shape, _dptr(d_b), _dptr(d_f), _dptr(d_co), _dptr(d_cx), _dptr(d_cy), n_corners, P)
     with _lib.lock():
-        return _picks_csr(lambda off, rows, cap, total: L.pmi_picks_shape_dev(
-            _dptr(d_x), tx, _dptr(d_y), ty, _dptr(table.rows), _dptr(table.keys), n, table.p, x0, y0, x1, y1, cell, CX,
-            CY, shape, _dptr(d_b), _dptr(d_f), _dptr(d_co), _dptr(d_cx), _dptr(d_cy), n_corners, P, off, rows, cap,
-            total, stream), P, device)
+        return _picks_csr("pmi_picks_shape_dev", head, P, device, stream)
 
 
 def picks_square(x, y, bounds, flags):
@@ -1166,11 +1219,10 @@ def similar_shift(table: "BlockTable", x, y, x_range, y_range_base, y_range_shif
     out = torch.zeros(3 * G, dtype=torch.float64, device=table.device)
     out_n = torch.zeros(G, dtype=torch.int32, device=table.device)
     with _lib.lock():
-        _lib.check(_lib.load().pmi_similar_shift_dev(
-            _dptr(d_x), tx, _dptr(d_y), ty, _dptr(table.rows), _dptr(table.keys), table.n, table.p, table.K, table.L,
-            _dptr(d_grid[0]), _dptr(d_grid[1]), n_x, _dptr(d_grid[2]), _dptr(d_grid[3]), _dptr(d_grid[4]), _dptr(d_grid[5]),
-            n_y, float(r2), float(gate), int(max_shifts), _dptr(out[:G]), _dptr(out[G:2 * G]), _dptr(out_n),
-            _dptr(out[2 * G:]), ctypes.c_void_p(table.stream)), "pmi_similar_shift_dev")
+        _lib.call("pmi_similar_shift_dev", _dptr(d_x), tx, _dptr(d_y), ty, _dptr(table.rows), _dptr(table.keys), table.n,
+                  table.p, table.K, table.L, _dptr(d_grid[0]), _dptr(d_grid[1]), n_x, _dptr(d_grid[2]), _dptr(d_grid[3]),
+                  _dptr(d_grid[4]), _dptr(d_grid[5]), n_y, float(r2), float(gate), int(max_shifts), _dptr(out[:G]),
+                  _dptr(out[G:2 * G]), _dptr(out_n), _dptr(out[2 * G:]), ctypes.c_void_p(table.stream))
         host = out.cpu().numpy()
         return host[:G].copy(), host[G:2 * G].copy(), out_n.cpu().numpy(), host[2 * G:].copy()
 
@@ -1183,8 +1235,8 @@ def similar_filter(cand_x, cand_y, pick_x, pick_y, d2: float, d: float) -> np.nd
     if cx.shape != cy.shape or px.shape != py.shape or cx.ndim != 1 or px.ndim != 1:
         raise ValueError("one x and one y per candidate and per pick")
     keep = np.zeros(len(cx), np.uint8)
-    _lib.check(_lib.load().pmi_similar_filter(_lib.ptr(cx), _lib.ptr(cy), len(cx), _lib.ptr(px), _lib.ptr(py), len(px),
-                                              float(d2), float(d), _lib.ptr(keep)), "pmi_similar_filter")
+    _lib.call("pmi_similar_filter", _lib.ptr(cx), _lib.ptr(cy), len(cx), _lib.ptr(px), _lib.ptr(py), len(px), float(d2),
+              float(d), _lib.ptr(keep))
     return keep.astype(bool)
 
 
@@ -1227,21 +1279,18 @@ def fiducials_drift(offsets, frame, columns, n_frames: int) -> np.ndarray:
         d_frame = frame.contiguous()
     else:
         d_frame = _to_device(_index_column(frame, "frame"))
-    cols = [_pick_column(c) for c in columns]
+    cols = [_float_column(c) for c in columns]
     M = int(offsets[-1])
-    if len(d_frame) != M or any(len(d) != M for d, _ in cols):
-        raise ValueError("frame and the columns must have offsets[-1] rows")
+    _check_rows(M, "frame and the columns must have offsets[-1] rows", d_frame, *[d for d, _ in cols])
     device = d_frame.device
     d_off = _to_device(offsets)
     out = torch.empty((F, len(cols)), dtype=torch.float64, device=device)
     ptrs = (ctypes.c_void_p * len(cols))(*[d.data_ptr() if M else None for d, _ in cols])
     types = (ctypes.c_int * len(cols))(*[t for _, t in cols])
     status = ctypes.c_int(0)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
     with _lib.lock():
-        _lib.check(_lib.load().pmi_fiducials_drift_dev(_dptr(d_off), P, _dptr(d_frame) if M else None, M, ptrs, types,
-                                                       len(cols), F, _dptr(out), ctypes.byref(status), stream),
-                   "pmi_fiducials_drift_dev")
+        _lib.call("pmi_fiducials_drift_dev", _dptr(d_off), P, _dptr(d_frame) if M else None, M, ptrs, types, len(cols), F,
+                  _dptr(out), ctypes.byref(status), ctypes.c_void_p(_stream(device)))
         if status.value & 1:
             raise IndexError(f"a frame is out of bounds for {F} frames")
         if status.value & 2:
@@ -1252,20 +1301,18 @@ def fiducials_drift(offsets, frame, columns, n_frames: int) -> np.ndarray:
 def fiducials_reduce(values, offsets) -> np.ndarray:
     """np.add.reduce of each run values[offsets[r] : offsets[r + 1]] in the values' own float type, by the workgroup
     sum of csrc/group_reduce.h (pmi_fiducials_reduce_dev); for the tests of that sum."""
-    import torch
     _lib.require_gpu()
     offsets = _fiducial_offsets(offsets)
-    d_v, t = _pick_column(values)
+    d_v, t = _float_column(values)
     if offsets[-1] > len(d_v):
         raise ValueError("offsets run past the values")
     R = len(offsets) - 1
-    out = torch.zeros(max(R, 1), dtype=d_v.dtype, device=d_v.device)
+    out = _out(d_v.device, d_v.dtype, R, zero=True)
     d_off = _to_device(offsets)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(d_v.device).cuda_stream)
     with _lib.lock():
-        _lib.check(_lib.load().pmi_fiducials_reduce_dev(_dptr(d_v) if len(d_v) else None, t, len(d_v), _dptr(d_off), R,
-                                                        _dptr(out), stream), "pmi_fiducials_reduce_dev")
-        return out[:R].cpu().numpy()
+        _lib.call("pmi_fiducials_reduce_dev", _dptr(d_v) if len(d_v) else None, t, len(d_v), _dptr(d_off), R, _dptr(out),
+                  ctypes.c_void_p(_stream(d_v.device)))
+        return out.cpu().numpy()
 
 
 # ---- nearest-neighbour distances (csrc/knn.hip, picasso/postprocess.py:3704-3739, picasso/spinna.py:696-747) ----
@@ -1280,10 +1327,7 @@ def knn_limit() -> int:
 
 def knn_points(X) -> np.ndarray:
     """A point set as the device takes it: float64, C-contiguous, (rows, 2 | 3)."""
-    X = np.ascontiguousarray(X, np.float64)
-    if X.ndim != 2 or X.shape[1] not in (2, 3):
-        raise ValueError(f"points must have shape (n, 2) or (n, 3), not {X.shape}")
-    return X
+    return _check_points(np.ascontiguousarray(X, np.float64))
 
 
 class KnnIndex:
@@ -1313,15 +1357,13 @@ class KnnIndex:
             self.points = X2
         self.m, self.dims = int(self.points.shape[0]), int(self.points.shape[1])
         lo, hi = np.ascontiguousarray(lo, np.float64), np.ascontiguousarray(hi, np.float64)
-        self.device = self.points.device
-        self.stream = torch.cuda.current_stream(self.device).cuda_stream
-        self.sorted = torch.empty((max(self.m, 1), self.dims), dtype=torch.float64, device=self.device)
+        self.device, self.stream = self.points.device, _stream(self.points.device)
+        self.sorted = _out(self.device, torch.float64, self.m, self.dims)
         self.start = torch.empty(max(self.m, 1) + 1, dtype=torch.int32, device=self.device)
         self.grid = _KnnGrid()
         with _lib.lock():
-            _lib.check(_lib.load().pmi_knn_order_dev(
-                _dptr(self.points), self.dims, self.m, _lib.ptr(lo), _lib.ptr(hi), int(k), _dptr(self.sorted),
-                _dptr(self.start), ctypes.byref(self.grid), ctypes.c_void_p(self.stream)), "pmi_knn_order_dev")
+            _lib.call("pmi_knn_order_dev", _dptr(self.points), self.dims, self.m, _lib.ptr(lo), _lib.ptr(hi), int(k),
+                      _dptr(self.sorted), _dptr(self.start), ctypes.byref(self.grid), ctypes.c_void_p(self.stream))
 
     def query_device(self, d_x1, k: int):
         """(n, k) float64 device tensor of the distances from the rows of the float64 device tensor `d_x1`."""
@@ -1330,12 +1372,11 @@ class KnnIndex:
                 or d_x1.dim() != 2 or int(d_x1.shape[1]) != self.dims or not d_x1.is_contiguous()):
             raise ValueError(f"queries must be a contiguous float64 tensor of shape (n, {self.dims}) on {self.device}")
         n = int(d_x1.shape[0])
-        out = torch.empty((max(n, 1), int(k)), dtype=torch.float64, device=self.device)
+        out = _out(self.device, torch.float64, n, int(k))
         with _lib.lock():
-            _lib.check(_lib.load().pmi_knn_query_dev(
-                _dptr(d_x1), self.dims, n, _dptr(self.sorted), _dptr(self.start), self.m, ctypes.byref(self.grid),
-                int(k), _dptr(out), ctypes.c_void_p(self.stream)), "pmi_knn_query_dev")
-        return out[:n]
+            _lib.call("pmi_knn_query_dev", _dptr(d_x1), self.dims, n, _dptr(self.sorted), _dptr(self.start), self.m,
+                      ctypes.byref(self.grid), int(k), _dptr(out), ctypes.c_void_p(self.stream))
+        return out
 
     def query(self, X1, k: int) -> np.ndarray:
         """(n, k) float64 distances from the rows of the host array `X1`, ascending, inf where the set has fewer rows."""
@@ -1348,33 +1389,12 @@ class KnnIndex:
 
 # ---- cluster centers (csrc/centers.hip, picasso/clusterer.py:694-897) ----
 CENTERS_MEAN, CENTERS_XSUM, CENTERS_FIRST, CENTERS_EVENTS = 0, 1, 2, 3
-_CENTERS_TYPES = {np.dtype("float32"): 0, np.dtype("float64"): 1, np.dtype("uint32"): 2, np.dtype("int32"): 3,
-                  np.dtype("uint64"): 4, np.dtype("int64"): 5}
 
 
 class _CentersColumn(ctypes.Structure):
     _fields_ = [("data", ctypes.c_void_p), ("weight", ctypes.c_void_p), ("sum", ctypes.c_void_p),
                 ("mean", ctypes.c_void_p), ("std", ctypes.c_void_p),
                 ("op", ctypes.c_int32), ("type", ctypes.c_int32), ("w_type", ctypes.c_int32)]
-
-
-def centers_type(dtype, floating: bool = False) -> int:
-    dt = np.dtype(dtype)
-    if dt not in _CENTERS_TYPES or (floating and dt.kind != "f"):
-        raise TypeError(f"unsupported column dtype {dt} for the cluster centers on the device")
-    return _CENTERS_TYPES[dt]
-
-
-def _centers_column(a, what: str) -> np.ndarray:
-    """A table column as the device takes it: bool and the narrow integers widened (to a type pandas would convert
-    to float64 all the same), float16 refused."""
-    a = np.asarray(a)
-    if a.dtype.kind == "b" or (a.dtype.kind in "iu" and a.dtype.itemsize < 4):
-        a = a.astype(np.int32 if a.dtype.kind != "u" else np.uint32)
-    if a.ndim != 1:
-        raise ValueError(f"{what} must be a column, not an array of shape {a.shape}")
-    centers_type(a.dtype)
-    return a
 
 
 class CenterGroups:
@@ -1388,24 +1408,28 @@ class CenterGroups:
         group = _index_column(group, "group")
         if group.ndim != 1 or len(group) == 0:
             raise ValueError("group must be a column of at least one row")
-        self.n = int(len(group))
-        self.g_min, self.g_max = int(group.min()), int(group.max())
-        self.group = _to_device(group)
-        self.device = self.group.device
-        self.stream = torch.cuda.current_stream(self.device).cuda_stream
-        self.rows = torch.empty(self.n, dtype=torch.int32, device=self.device)
-        self.start = torch.empty(self.n + 1, dtype=torch.int32, device=self.device)
+        self._reside(group)
         unique = torch.empty(self.n, dtype=torch.int64, device=self.device)
         G = ctypes.c_int64(0)
         with _lib.lock():
-            _lib.check(_lib.load().pmi_centers_order_dev(
-                _dptr(self.group), self.n, self.g_min, self.g_max, _dptr(self.rows), _dptr(self.start), _dptr(unique),
-                ctypes.byref(G), ctypes.c_void_p(self.stream)), "pmi_centers_order_dev")
+            _lib.call("pmi_centers_order_dev", _dptr(self.group), self.n, self.g_min, self.g_max, _dptr(self.rows),
+                      _dptr(self.start), _dptr(unique), ctypes.byref(G), ctypes.c_void_p(self.stream))
             self.n_groups = int(G.value)
             self.unique = unique[:self.n_groups].cpu().numpy()
             self.offsets = self.start[:self.n_groups + 1].cpu().numpy()
         self.n_locs = np.diff(self.offsets).astype(np.int64)
-        self._cache = {}
+
+    def _reside(self, group):
+        """What every order by labels keeps: the checked int64 ``group`` column on the device with its range, where the
+        table lives, room for the order, and the uploads of its columns."""
+        import torch
+        self.n = int(len(group))
+        self.g_min, self.g_max = int(group.min()), int(group.max())
+        self.group = _to_device(group)
+        self.device, self.stream = self.group.device, _stream(self.group.device)
+        self.rows = torch.empty(self.n, dtype=torch.int32, device=self.device)
+        self.start = torch.empty(self.n + 1, dtype=torch.int32, device=self.device)
+        self._cache = _Uploads(self.n)
 
     def order(self) -> np.ndarray:
         """The int64 stable permutation into group order."""
@@ -1413,12 +1437,7 @@ class CenterGroups:
 
     def _dev(self, a):
         """One upload per host column, however many statistics read it."""
-        key = (a.__array_interface__["data"][0], a.strides, a.dtype.str)      # two views of one column are one upload
-        if key not in self._cache:
-            if len(a) != self.n:
-                raise ValueError("every column must have one entry per row of the table")
-            self._cache[key] = (a, _to_device(a))
-        return self._cache[key][1]
+        return self._cache.column(a)
 
     def weights(self, lpx, lpy):
         """Device column ``1.0 / (lpx + lpy) ** 2`` in NumPy's result type of the two -> (tensor, dtype)."""
@@ -1427,12 +1446,11 @@ class CenterGroups:
         dt = np.result_type(lpx.dtype, lpy.dtype)
         code = centers_type(dt, True)
         d_x, d_y = _to_device(lpx, dt), _to_device(lpy, dt)
-        if len(lpx) != self.n or len(lpy) != self.n:
-            raise ValueError("every column must have one entry per row of the table")
-        w = torch.empty(self.n, dtype=torch.float32 if code == 0 else torch.float64, device=self.device)
+        _check_rows(self.n, _PER_ROW, lpx, lpy)
+        w = torch.empty(self.n, dtype=d_x.dtype, device=self.device)
         with _lib.lock():
-            _lib.check(_lib.load().pmi_centers_weights_dev(_dptr(d_x), _dptr(d_y), code, self.n, _dptr(w),
-                                                           ctypes.c_void_p(self.stream)), "pmi_centers_weights_dev")
+            _lib.call("pmi_centers_weights_dev", _dptr(d_x), _dptr(d_y), code, self.n, _dptr(w),
+                      ctypes.c_void_p(self.stream))
         return w, np.dtype(dt)
 
     def stats(self, requests):
@@ -1440,26 +1458,23 @@ class CenterGroups:
         CENTERS_MEAN and ignored otherwise; ``column`` a host column or the (tensor, dtype) of ``weights()``, which
         is also what ``weight`` takes.
         -> one dict of arrays per request ("sum" holds the result of the other ops)."""
-        import torch
         G = self.n_groups
-        desc = (_CentersColumn * max(len(requests), 1))()
-        keep, outs = [], []
-        for i, (op, column, weight, wants) in enumerate(requests):
+        rows, outs = [], []
+        for op, column, weight, wants in requests:
             if isinstance(column, tuple):                   # already on the device: what weights() returned
                 d, dtype = column
             else:
                 column = _centers_column(column, "a statistics column")
                 d, dtype = self._dev(column), column.dtype
             code = centers_type(dtype, op == CENTERS_XSUM)
-            w_code, w_ptr = 0, None
+            w_code, w_t = 0, None
             if op == CENTERS_MEAN:
-                acc = np.dtype(np.float32) if code == 0 else np.dtype(np.float64)
+                acc = np.dtype(np.float32) if dtype == np.float32 else np.dtype(np.float64)
                 types = {"sum": acc, "mean": acc, "std": np.dtype(np.float64)}
                 wants = tuple(wants)
             elif op == CENTERS_XSUM:
                 w_t, w_dt = weight
-                w_code, w_ptr = centers_type(w_dt, True), w_t.data_ptr()
-                keep.append(w_t)
+                w_code = centers_type(w_dt, True)
                 types, wants = {"sum": np.promote_types(dtype, w_dt)}, ("sum",)
             elif op == CENTERS_FIRST:
                 types, wants = {"sum": np.dtype(dtype)}, ("sum",)
@@ -1469,13 +1484,11 @@ class CenterGroups:
                 raise ValueError(f"unknown statistics op {op}")
             out = {k: _to_device(np.zeros(G, types[k])) for k in wants}
             outs.append((out, types))
-            keep.append(d)
-            desc[i] = _CentersColumn(d.data_ptr(), w_ptr, *(out[k].data_ptr() if k in out else None
-                                                             for k in ("sum", "mean", "std")), int(op), code, w_code)
+            rows.append((d, w_t, out.get("sum"), out.get("mean"), out.get("std"), int(op), code, w_code))
+        table = _Table(_CentersColumn, rows)
         with _lib.lock():
-            _lib.check(_lib.load().pmi_centers_stats_dev(
-                _dptr(self.rows), _dptr(self.start), self.n, G, ctypes.cast(desc, ctypes.c_void_p), len(requests),
-                ctypes.c_void_p(self.stream)), "pmi_centers_stats_dev")
+            _lib.call("pmi_centers_stats_dev", _dptr(self.rows), _dptr(self.start), self.n, G, table.ptr, table.count,
+                      ctypes.c_void_p(self.stream))
             return [{k: t.cpu().numpy().view(types[k]) for k, t in out.items()} for out, types in outs]
 
     def hull_areas(self, x, y) -> np.ndarray:
@@ -1486,9 +1499,8 @@ class CenterGroups:
         d_x, d_y = self._dev(x), self._dev(y)
         area = torch.zeros(self.n_groups, dtype=torch.float64, device=self.device)
         with _lib.lock():
-            _lib.check(_lib.load().pmi_centers_hull_dev(
-                _dptr(d_x), tx, _dptr(d_y), ty, _dptr(self.group), self.g_min, self.g_max, _dptr(self.start), self.n,
-                self.n_groups, _dptr(area), ctypes.c_void_p(self.stream)), "pmi_centers_hull_dev")
+            _lib.call("pmi_centers_hull_dev", _dptr(d_x), tx, _dptr(d_y), ty, _dptr(self.group), self.g_min, self.g_max,
+                      _dptr(self.start), self.n, self.n_groups, _dptr(area), ctypes.c_void_p(self.stream))
             return area.cpu().numpy()
 
 
@@ -1575,9 +1587,8 @@ class AreaImages:
         self.geom = torch.zeros(G * _AREAS_GEOM.itemsize, dtype=torch.uint8, device=groups.device)
         bin_f32 = int(np.asarray(bin_xy).dtype == np.float32)
         with _lib.lock():
-            _lib.check(_lib.load().pmi_areas_shape_dev(
-                ctypes.byref(self.cols), _dptr(groups.rows), _dptr(groups.start), groups.n, G, float(bin_xy), float(bin_z),
-                bin_f32, _dptr(self.geom), ctypes.c_void_p(groups.stream)), "pmi_areas_shape_dev")
+            _lib.call("pmi_areas_shape_dev", ctypes.byref(self.cols), _dptr(groups.rows), _dptr(groups.start), groups.n, G,
+                      float(bin_xy), float(bin_z), bin_f32, _dptr(self.geom), ctypes.c_void_p(groups.stream))
             self.host_geom = self.geom.cpu().numpy().view(_AREAS_GEOM)
         self.lens = self.host_geom["len"][:, :self.dims]
         self.bins = areas_bins(groups.unique, self.lens)
@@ -1591,11 +1602,10 @@ class AreaImages:
         d_list = torch.from_numpy(np.ascontiguousarray(listed, np.int32)).to(groups.device)
         d_off = None if offsets is None else torch.from_numpy(np.ascontiguousarray(offsets, np.int64)).to(groups.device)
         with _lib.lock():
-            _lib.check(_lib.load().pmi_areas_image_dev(
-                ctypes.byref(self.cols), _dptr(groups.rows), _dptr(groups.start), groups.n, groups.n_groups,
-                _dptr(self.geom), _dptr(d_list), _dptr(d_off), len(listed), _dptr(scratch),
-                0 if scratch is None else int(scratch.numel()), _dptr(weights), _dptr(area), int(want),
-                _dptr(want_image), ctypes.c_void_p(groups.stream)), "pmi_areas_image_dev")
+            _lib.call("pmi_areas_image_dev", ctypes.byref(self.cols), _dptr(groups.rows), _dptr(groups.start), groups.n,
+                      groups.n_groups, _dptr(self.geom), _dptr(d_list), _dptr(d_off), len(listed), _dptr(scratch),
+                      0 if scratch is None else int(scratch.numel()), _dptr(weights), _dptr(area), int(want),
+                      _dptr(want_image), ctypes.c_void_p(groups.stream))
 
     def areas(self, image_of=None, force_scratch: bool = False):
         """float32 area (count / 4) or volume (count / (16 / 5)) of every group; 0 for a group without bins.  With
@@ -1609,7 +1619,7 @@ class AreaImages:
         want = -1 if image_of is None else int(image_of)
         want_image = None
         if want >= 0:
-            want_image = torch.zeros(max(int(self.bins[want]), 1), dtype=torch.float64, device=device)
+            want_image = _out(device, torch.float64, self.bins[want], zero=True)
         small = np.flatnonzero((self.bins > 0) & (self.bins <= lds_bins))
         large = np.flatnonzero(self.bins > lds_bins)
         if len(small):
@@ -1628,7 +1638,7 @@ class AreaImages:
         out = area.cpu().numpy()
         if want < 0:
             return out
-        return out, want_image.cpu().numpy()[:int(self.bins[want])].reshape(self.shape(want))
+        return out, want_image.cpu().numpy().reshape(self.shape(want))
 
 
 # ---- dark times and group properties (csrc/kinetics.hip, picasso/postprocess.py:1985-2004, :3580-3649) ----
@@ -1654,50 +1664,44 @@ class DarkTable:
             raise ValueError("frame, group and last_frame must have one length, of at least one row")
         self.max_frame = int(frame.max())
         self.frame, self.group, self.last = _to_device(frame), _to_device(group), _to_device(last_frame)
-        self.device = self.frame.device
-        self.stream = torch.cuda.current_stream(self.device).cuda_stream
+        self.device, self.stream = self.frame.device, _stream(self.frame.device)
         self.rows = torch.empty(self.n, dtype=torch.int32, device=self.device)
         self.last_sorted = torch.empty(self.n, dtype=torch.int64, device=self.device)
         self.run = torch.empty(self.n, dtype=torch.int32, device=self.device)
         self.start = torch.empty(self.n + 1, dtype=torch.int32, device=self.device)
         with _lib.lock():
-            _lib.check(_lib.load().pmi_kinetics_dark_order_dev(
-                _dptr(self.last), _dptr(self.group), self.n, int(last_frame.min()), int(last_frame.max()),
-                int(group.min()), int(group.max()), _dptr(self.rows), _dptr(self.last_sorted), _dptr(self.run),
-                _dptr(self.start), ctypes.c_void_p(self.stream)), "pmi_kinetics_dark_order_dev")
+            _lib.call("pmi_kinetics_dark_order_dev", _dptr(self.last), _dptr(self.group), self.n, int(last_frame.min()),
+                      int(last_frame.max()), int(group.min()), int(group.max()), _dptr(self.rows),
+                      _dptr(self.last_sorted), _dptr(self.run), _dptr(self.start), ctypes.c_void_p(self.stream))
 
     def search(self) -> np.ndarray:
         """int64 dark time of every row, -1 where there is none."""
         import torch
         dark = torch.empty(self.n, dtype=torch.int64, device=self.device)
         with _lib.lock():
-            _lib.check(_lib.load().pmi_kinetics_dark_search_dev(
-                _dptr(self.frame), _dptr(self.rows), _dptr(self.last_sorted), _dptr(self.run), _dptr(self.start), self.n,
-                self.max_frame, _dptr(dark), ctypes.c_void_p(self.stream)), "pmi_kinetics_dark_search_dev")
+            _lib.call("pmi_kinetics_dark_search_dev", _dptr(self.frame), _dptr(self.rows), _dptr(self.last_sorted),
+                      _dptr(self.run), _dptr(self.start), self.n, self.max_frame, _dptr(dark),
+                      ctypes.c_void_p(self.stream))
             return dark.cpu().numpy()
+
+
+def _float64_pair(groups: "CenterGroups"):
+    """Two float64 device outputs of one entry per group of ``groups``."""
+    import torch
+    return tuple(torch.empty(groups.n_groups, dtype=torch.float64, device=groups.device) for _ in range(2))
 
 
 def group_mean_std(groups: "CenterGroups", columns):
     """pandas' ``Series.mean()`` and ``Series.std()`` of every host column in ``columns`` per group of ``groups``
     (pmi_kinetics_stats_dev) -> a list of (float64 mean, float64 std), one pair of arrays per column."""
-    import torch
-    G, out = groups.n_groups, []
+    out = []
     columns = [_centers_column(c, "a statistics column") for c in columns]
-    for lo in range(0, len(columns), KINETICS_MAX_COLUMNS):
-        part = columns[lo:lo + KINETICS_MAX_COLUMNS]
-        desc = (_KineticsColumn * len(part))()
-        keep = []
-        for i, c in enumerate(part):
-            d = groups._dev(c)
-            mean = torch.empty(G, dtype=torch.float64, device=groups.device)
-            std = torch.empty(G, dtype=torch.float64, device=groups.device)
-            keep.append((d, mean, std))
-            desc[i] = _KineticsColumn(d.data_ptr(), mean.data_ptr(), std.data_ptr(), centers_type(c.dtype))
+    rows = [(groups._dev(c), *_float64_pair(groups), centers_type(c.dtype)) for c in columns]
+    for table in _Table.chunks(_KineticsColumn, rows, KINETICS_MAX_COLUMNS):
         with _lib.lock():
-            _lib.check(_lib.load().pmi_kinetics_stats_dev(
-                _dptr(groups.rows), _dptr(groups.start), groups.n, G, ctypes.cast(desc, ctypes.c_void_p), len(part),
-                ctypes.c_void_p(groups.stream)), "pmi_kinetics_stats_dev")
-            out += [(mean.cpu().numpy(), std.cpu().numpy()) for _, mean, std in keep]
+            _lib.call("pmi_kinetics_stats_dev", _dptr(groups.rows), _dptr(groups.start), groups.n, groups.n_groups,
+                      table.ptr, table.count, ctypes.c_void_p(groups.stream))
+            out += [(mean.cpu().numpy(), std.cpu().numpy()) for _, mean, std, _ in table.rows]
     return out
 
 
@@ -1725,23 +1729,17 @@ class CombineGroups(CenterGroups):
         group, cluster = _index_column(group, "group"), _index_column(cluster, "cluster")
         if group.ndim != 1 or cluster.ndim != 1 or len(group) == 0 or len(cluster) != len(group):
             raise ValueError("group and cluster must be columns of one length, of at least one row")
-        self.n = int(len(group))
-        self.g_min, self.g_max = int(group.min()), int(group.max())
+        self._reside(group)
         self.c_min, self.c_max = int(cluster.min()), int(cluster.max())
-        self.group, self.cluster = _to_device(group), _to_device(cluster)
-        self.device = self.group.device
-        self.stream = torch.cuda.current_stream(self.device).cuda_stream
-        self.rows = torch.empty(self.n, dtype=torch.int32, device=self.device)
-        self.start = torch.empty(self.n + 1, dtype=torch.int32, device=self.device)
+        self.cluster = _to_device(cluster)
         self.group_start = torch.empty(self.n + 1, dtype=torch.int32, device=self.device)
         seg_group = torch.empty(self.n, dtype=torch.int64, device=self.device)
         seg_cluster = torch.empty(self.n, dtype=torch.int64, device=self.device)
         S, G = ctypes.c_int64(0), ctypes.c_int64(0)
         with _lib.lock():
-            _lib.check(_lib.load().pmi_combine_order_dev(
-                _dptr(self.group), _dptr(self.cluster), self.n, self.g_min, self.g_max, self.c_min, self.c_max,
-                _dptr(self.rows), _dptr(self.start), _dptr(seg_group), _dptr(seg_cluster), _dptr(self.group_start),
-                ctypes.byref(S), ctypes.byref(G), ctypes.c_void_p(self.stream)), "pmi_combine_order_dev")
+            _lib.call("pmi_combine_order_dev", _dptr(self.group), _dptr(self.cluster), self.n, self.g_min, self.g_max,
+                      self.c_min, self.c_max, _dptr(self.rows), _dptr(self.start), _dptr(seg_group), _dptr(seg_cluster),
+                      _dptr(self.group_start), ctypes.byref(S), ctypes.byref(G), ctypes.c_void_p(self.stream))
             self.n_groups = int(S.value)
             self.n_outer = int(G.value)
             self.unique = seg_group[:self.n_groups].cpu().numpy()
@@ -1749,15 +1747,14 @@ class CombineGroups(CenterGroups):
             self.offsets = self.start[:self.n_groups + 1].cpu().numpy()
             self.group_offsets = self.group_start[:self.n_outer + 1].cpu().numpy()
         self.n_locs = np.diff(self.offsets).astype(np.int64)
-        self._cache = {}
 
     def hull_areas(self, x, y):
         raise NotImplementedError("convex hulls are per label of one column: use CenterGroups")
 
 
-def _combine_floats(a, what: str, dtype=None) -> np.ndarray:
+def _combine_floats(a, what: str) -> np.ndarray:
     """A host column for the weighted average: 1-D, float32 or float64, contiguous."""
-    a = np.ascontiguousarray(a if dtype is None else np.asarray(a).astype(dtype, copy=False))
+    a = np.ascontiguousarray(a)
     if a.ndim != 1 or a.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
         raise TypeError(f"{what} must be a float32 or float64 column, not {a.dtype} of shape {a.shape}")
     return a
@@ -1768,42 +1765,32 @@ def combine_stats(groups: "CombineGroups", moments=(), averages=()):
     ``Series.mean()`` and ``Series.std()``; for every (column, weights) pair in ``averages``, both float32 or both
     float64 (promote as ``np.average`` does before the call), ``np.average(column, weights=weights)`` and the sum of
     the weights.  -> (list of (float64 mean, float64 std), list of (float64 average, float64 weight sum))."""
-    import torch
     if not isinstance(groups, CombineGroups):
         raise TypeError("groups must be a CombineGroups")
-    S = groups.n_groups
     jobs = []
     for c in moments:
         c = _centers_column(c, "a statistics column")
-        if len(c) != groups.n:
-            raise ValueError("every column must have one entry per row of the table")
-        jobs.append(("moments", np.ascontiguousarray(c), None))
+        _check_rows(groups.n, _PER_ROW, c)
+        jobs.append((np.ascontiguousarray(c), None))
     for x, w in averages:
         x, w = _combine_floats(x, "an averaged column"), _combine_floats(w, "the weights")
         if x.dtype != w.dtype or len(x) != groups.n or len(w) != groups.n:
             raise ValueError("an averaged column and its weights must have one floating type and one entry per row")
-        jobs.append(("average", x, w))
-    out = []
-    for lo in range(0, len(jobs), COMBINE_MAX_COLUMNS):
-        part = jobs[lo:lo + COMBINE_MAX_COLUMNS]
-        desc = (_CombineColumn * len(part))()
-        keep = []
-        for i, (kind, c, w) in enumerate(part):
-            d = groups._dev(c)
-            d_w = groups._dev(w) if w is not None else None
-            a = torch.empty(S, dtype=torch.float64, device=groups.device)
-            b = torch.empty(S, dtype=torch.float64, device=groups.device)
-            keep.append((d, d_w, a, b))
-            if kind == "moments":
-                desc[i] = _CombineColumn(d.data_ptr(), None, a.data_ptr(), b.data_ptr(), None, None, centers_type(c.dtype))
-            else:
-                desc[i] = _CombineColumn(d.data_ptr(), d_w.data_ptr(), None, None, a.data_ptr(), b.data_ptr(),
-                                         centers_type(c.dtype, True))
+        jobs.append((x, w))
+    rows, pairs, out = [], [], []
+    for c, w in jobs:
+        a, b = _float64_pair(groups)
+        pairs.append((a, b))
+        if w is None:                                       # the moments: mean and std
+            rows.append((groups._dev(c), None, a, b, None, None, centers_type(c.dtype)))
+        else:                                               # the average and the weight sum
+            rows.append((groups._dev(c), groups._dev(w), None, None, a, b, centers_type(c.dtype, True)))
+    for lo, table in enumerate(_Table.chunks(_CombineColumn, rows, COMBINE_MAX_COLUMNS)):
         with _lib.lock():
-            _lib.check(_lib.load().pmi_combine_stats_dev(
-                _dptr(groups.rows), _dptr(groups.start), groups.n, S, ctypes.cast(desc, ctypes.c_void_p), len(part),
-                ctypes.c_void_p(groups.stream)), "pmi_combine_stats_dev")
-            out += [(a.cpu().numpy(), b.cpu().numpy()) for _, _, a, b in keep]
+            _lib.call("pmi_combine_stats_dev", _dptr(groups.rows), _dptr(groups.start), groups.n, groups.n_groups,
+                      table.ptr, table.count, ctypes.c_void_p(groups.stream))
+            done = pairs[lo * COMBINE_MAX_COLUMNS:(lo + 1) * COMBINE_MAX_COLUMNS]
+            out += [(a.cpu().numpy(), b.cpu().numpy()) for a, b in done]
     return out[:len(moments)], out[len(moments):]
 
 
@@ -1824,10 +1811,9 @@ def combine_min_distances(groups: "CombineGroups", points):
     best = torch.empty(groups.n, dtype=torch.float64, device=groups.device)
     best_xy = torch.empty(groups.n, dtype=torch.float64, device=groups.device) if dims == 3 else None
     with _lib.lock():
-        _lib.check(_lib.load().pmi_combine_mindist_dev(
-            _dptr(d_points), dims, _dptr(groups.rows), _dptr(groups.start), _dptr(groups.group_start), groups.n,
-            groups.n_groups, groups.n_outer, _dptr(best), _dptr(best_xy) if best_xy is not None else None,
-            ctypes.c_void_p(groups.stream)), "pmi_combine_mindist_dev")
+        _lib.call("pmi_combine_mindist_dev", _dptr(d_points), dims, _dptr(groups.rows), _dptr(groups.start),
+                  _dptr(groups.group_start), groups.n, groups.n_groups, groups.n_outer, _dptr(best), _dptr(best_xy),
+                  ctypes.c_void_p(groups.stream))
         return best.cpu().numpy(), (best_xy.cpu().numpy() if best_xy is not None else None)
 
 
@@ -1843,7 +1829,7 @@ def average_limits():
     """(AVERAGE_LDS_BINS, AVERAGE_LIST, AVERAGE_MAX_PIXELS) as the loaded library has them; a library built with other
     bounds is refused."""
     vals = [ctypes.c_int(0) for _ in range(3)]
-    _lib.check(_lib.load().pmi_average_limits(*(ctypes.byref(v) for v in vals)), "pmi_average_limits")
+    _lib.call("pmi_average_limits", *(ctypes.byref(v) for v in vals))
     limits = tuple(int(v.value) for v in vals)
     if limits != (AVERAGE_LDS_BINS, AVERAGE_LIST, AVERAGE_MAX_PIXELS):
         raise _lib.HipBackendError(f"libpicasso_hip was built with the averaging bounds {limits}, this package with "
@@ -1912,25 +1898,24 @@ class AverageAligner:
         stream = ctypes.c_void_p(groups.stream)
         ms = {}
 
-        def timed(name, call):
+        def timed(name, call, *args):
             t0, t1 = ctypes.c_void_p(), ctypes.c_void_p()
-            _lib.check(L.pmi_event_create(ctypes.byref(t0)), "pmi_event_create")
-            _lib.check(L.pmi_event_create(ctypes.byref(t1)), "pmi_event_create")
+            _lib.call("pmi_event_create", ctypes.byref(t0))
+            _lib.call("pmi_event_create", ctypes.byref(t1))
             try:
-                _lib.check(L.pmi_event_record(t0, stream), "pmi_event_record")
-                call()
-                _lib.check(L.pmi_event_record(t1, stream), "pmi_event_record")
+                _lib.call("pmi_event_record", t0, stream)
+                _lib.call(call, *args, stream)
+                _lib.call("pmi_event_record", t1, stream)
                 took = ctypes.c_float(0)
-                _lib.check(L.pmi_event_elapsed_ms(t0, t1, ctypes.byref(took)), "pmi_event_elapsed_ms")
+                _lib.call("pmi_event_elapsed_ms", t0, t1, ctypes.byref(took))
                 ms[name] = float(took.value)
             finally:
                 L.pmi_event_destroy(t0)
                 L.pmi_event_destroy(t1)
 
         with _lib.lock():
-            timed("image", lambda: _lib.check(L.pmi_average_image_dev(
-                _dptr(d_x), _dptr(d_y), n, n_pixel, lo, hi, ov, sub_f32, mul_f32, _dptr(image), _dptr(dropped), stream),
-                "pmi_average_image_dev"))
+            timed("image", "pmi_average_image_dev", _dptr(d_x), _dptr(d_y), n, n_pixel, lo, hi, ov, sub_f32, mul_f32,
+                  _dptr(image), _dptr(dropped))
             host_image = image.cpu().numpy().reshape(n_pixel, n_pixel)
             if int(dropped.cpu()[0]):
                 raise IndexError(f"index {n_pixel} is out of bounds for axis 0 with size {n_pixel}")
@@ -1938,16 +1923,14 @@ class AverageAligner:
             if self.max_group * top >= 2 ** 31:
                 raise ValueError(f"a group of {self.max_group} rows against an average image that peaks at {top}: the "
                                  "correlation could exceed 32 bits")
-            timed("align", lambda: _lib.check(L.pmi_average_align_dev(
-                _dptr(d_x), _dptr(d_y), _dptr(groups.rows), _dptr(groups.start), n, G, n_pixel, lo, hi, ov,
-                _dptr(self.d_cos), _dptr(self.d_sin), self.n_angles, chunks, _dptr(image), use_lds, _dptr(parts),
-                _dptr(dropped), stream), "pmi_average_align_dev"))
+            timed("align", "pmi_average_align_dev", _dptr(d_x), _dptr(d_y), _dptr(groups.rows), _dptr(groups.start), n, G,
+                  n_pixel, lo, hi, ov, _dptr(self.d_cos), _dptr(self.d_sin), self.n_angles, chunks, _dptr(image), use_lds,
+                  _dptr(parts), _dptr(dropped))
             if int(dropped.cpu()[0]):
                 raise IndexError(f"index {n_pixel} is out of bounds for axis 0 with size {n_pixel}")
-            timed("apply", lambda: _lib.check(L.pmi_average_apply_dev(
-                _dptr(d_x), _dptr(d_y), _dptr(groups.rows), _dptr(groups.start), n, G, n_pixel, ov, _dptr(self.d_cos),
-                _dptr(self.d_sin), self.n_angles, _dptr(parts), chunks, _dptr(choice), _dptr(x_out), _dptr(y_out), stream),
-                "pmi_average_apply_dev"))
+            timed("apply", "pmi_average_apply_dev", _dptr(d_x), _dptr(d_y), _dptr(groups.rows), _dptr(groups.start), n, G,
+                  n_pixel, ov, _dptr(self.d_cos), _dptr(self.d_sin), self.n_angles, _dptr(parts), chunks, _dptr(choice),
+                  _dptr(x_out), _dptr(y_out))
             return {"image": host_image, "choice": choice.cpu().numpy().reshape(G, 3), "x": x_out.cpu().numpy(),
                     "y": y_out.cpu().numpy(), "chunks": chunks, "ms": ms}
 
@@ -1980,10 +1963,9 @@ def render_hist_device(x, y, oversampling, y_min, x_min, y_max, x_max):
     """The histogram render (``render_arrays`` without widths) that stays on the device -> (n, float32 device tensor)."""
     import torch
     _lib.require_gpu()
-    L = _lib.load()
     ny, nx = ctypes.c_int64(), ctypes.c_int64()
-    _lib.check(L.pmi_render_dims(float(oversampling), float(y_min), float(x_min), float(y_max), float(x_max),
-                                 ctypes.byref(ny), ctypes.byref(nx)), "pmi_render_dims")
+    _lib.call("pmi_render_dims", float(oversampling), float(y_min), float(x_min), float(y_max), float(x_max),
+              ctypes.byref(ny), ctypes.byref(nx))
     if ny.value <= 0 or nx.value <= 0:
         raise ValueError("empty viewport")
     if max(ny.value, nx.value) > FRC_MAX_SIDE + 1:
@@ -1992,9 +1974,8 @@ def render_hist_device(x, y, oversampling, y_min, x_min, y_max, x_max):
     image = torch.empty((ny.value, nx.value), dtype=torch.float32, device=d_x.device)
     count = torch.zeros(1, dtype=torch.int64, device=d_x.device)
     with _lib.lock():
-        _lib.check(L.pmi_render_hist_dev(_dptr(d_x), _dptr(d_y), len(d_x), float(oversampling), float(y_min), float(x_min),
-                                         float(y_max), float(x_max), _dptr(image), ny.value, nx.value, _dptr(count), None),
-                   "pmi_render_hist_dev")
+        _lib.call("pmi_render_hist_dev", _dptr(d_x), _dptr(d_y), len(d_x), float(oversampling), float(y_min), float(x_min),
+                  float(y_max), float(x_max), _dptr(image), ny.value, nx.value, _dptr(count), None)
         n = int(count.cpu()[0])
     return n, image
 
@@ -2007,7 +1988,6 @@ def frc_arrays(im1, im2, w):
     curve: milliseconds by device events)."""
     import torch
     _lib.require_gpu()
-    L = _lib.load()
     if tuple(im1.shape) != tuple(im2.shape) or len(im1.shape) != 2 or im1.shape[0] != im1.shape[1]:
         raise ValueError(f"two square images of one side are needed, not {tuple(im1.shape)} and {tuple(im2.shape)}")
     m = int(im1.shape[0])
@@ -2035,8 +2015,8 @@ def frc_arrays(im1, im2, w):
     ms = (ctypes.c_float * 4)()
     torch.cuda.current_stream().synchronize()
     with _lib.lock():
-        _lib.check(L.pmi_frc_curve_dev(_dptr(d1), _dptr(d2), m, _dptr(d_w), _dptr(sums), _dptr(curve), _dptr(m1), _dptr(m2),
-                                       ctypes.cast(ms, ctypes.c_void_p), None), "pmi_frc_curve_dev")
+        _lib.call("pmi_frc_curve_dev", _dptr(d1), _dptr(d2), m, _dptr(d_w), _dptr(sums), _dptr(curve), _dptr(m1), _dptr(m2),
+                  ctypes.cast(ms, ctypes.c_void_p), None)
     return {"images": (m1.cpu().numpy(), m2.cpu().numpy()), "sums": sums.cpu().numpy().reshape(3, rings),
             "curve": curve.cpu().numpy(), "ms": dict(zip(("window", "fft", "rings", "curve"), (float(v) for v in ms)))}
 
@@ -2053,6 +2033,5 @@ def radial_sum_array(image) -> np.ndarray:
     _lib.require_gpu()
     out = np.empty(n // 2 + 1, image.dtype)
     with _lib.lock():
-        rc = _lib.load().pmi_radial_sum(_lib.ptr(image), RADIAL_TYPES[image.dtype], n, _lib.ptr(out))
-    _lib.check(rc, "pmi_radial_sum")
+        _lib.call("pmi_radial_sum", _lib.ptr(image), RADIAL_TYPES[image.dtype], n, _lib.ptr(out))
     return out
