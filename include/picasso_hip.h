@@ -38,6 +38,8 @@
  *                      fitting_method="gausslq"
  *   pmi_render_*       picasso/render.py:37-175 render -> :798-853 _render_hist,
  *                      :1020-1070 _render_gaussian (ang=None), :177-232, :451-467, :494-575
+ *   pmi_blur*, pmi_render_blurred  picasso/render.py:1413-1460 _fftconvolve under :1349-1410
+ *                      _render_smooth and :1249-1319 _render_convolve
  *   pmi_xcorr, pmi_rcc_pairs   picasso/imageprocess.py:27-50 xcorr, :53-161
  *                      get_image_shift (up to its curve_fit), :164-217 rcc
  *   pmi_localize_mle_dev    picasso/localize.py:1682-1815 localize with
@@ -406,6 +408,33 @@ int pmi_render_gaussian_dev(const float *d_x, const float *d_y, const float *d_l
                             int64_t N, double oversampling, double y_min, double x_min, double y_max,
                             double x_max, double min_blur_width, int iso, float *d_image, int64_t ny,
                             int64_t nx, int64_t *d_n_rendered, void *stream);
+
+/* ---- image blur (picasso/render.py:1413-1460 _fftconvolve; the "smooth" and "convolve" renders) --- *
+ * A separable blur of a float32 image of ny x nx pixels, axis 0 (y, weights wy, radius ry) first, then axis 1
+ * (x, wx, rx).  An axis whose weight pointer is NULL is skipped; a radius of 0 multiplies by its one weight.  Each
+ * weight vector holds 2 r + 1 float64 values and is taken to be symmetric (only w[0 .. r] are read).  The image is
+ * extended by zeros (scipy's mode="constant", cval=0); a radius beyond the image side is legal.  Per axis and output
+ * sample l of a line, in float64 and in this order, contraction off:
+ *     tmp = line[l] * w[r];   for j = r, r - 1, ..., 1:   tmp += (line[l - j] + line[l + j]) * w[r - j];
+ * which is scipy.ndimage.correlate1d for symmetric weights.
+ *   round_between != 0  tmp is rounded to float32 after each axis, the second axis reads the float32 values back:
+ *                       scipy.ndimage.gaussian_filter(output=float32, mode="constant") in every bit when the weights
+ *                       are its _gaussian_kernel1d; `scale` is not used.  With both axes skipped the output is a copy.
+ *   round_between == 0  float64 between the axes, then tmp * scale and one rounding to float32: the direct sum that
+ *                       stands in for the reference's single-precision FFT convolution (weights = its window
+ *                       functions, scale = 1 / kernel.sum()).
+ * Sides are limited as the render's are (below 2^31, at most 2^31 - 1 tiles of 32 x 32 pixels).  d_in and d_out
+ * must not overlap.  The _dev form is asynchronous, all pointers device pointers, its intermediate image in the
+ * library's scratch.  pmi_render_blurred is pmi_render_hist followed by pmi_blur without the histogram leaving the
+ * device: only the blurred image and *n_rendered come back.                                                  */
+int pmi_blur_dev(const float *d_in, float *d_out, int64_t ny, int64_t nx, const double *d_wy, int64_t ry,
+                 const double *d_wx, int64_t rx, int round_between, double scale, void *stream);
+int pmi_blur(const float *in, float *out, int64_t ny, int64_t nx, const double *wy, int64_t ry,
+             const double *wx, int64_t rx, int round_between, double scale);
+int pmi_render_blurred(const float *x, const float *y, int64_t N, double oversampling,
+                       double y_min, double x_min, double y_max, double x_max,
+                       const double *wy, int64_t ry, const double *wx, int64_t rx, int round_between, double scale,
+                       float *image, int64_t ny, int64_t nx, int64_t *n_rendered);
 
 /* ---- cross-correlation for RCC undrift (picasso/imageprocess.py:27-217) ---- *
  * pmi_xcorr: out = fftshift(real(ifft2(fft2(A) * conj(fft2(B))))) / sqrt(Y*X),

@@ -7,6 +7,7 @@ and raises if the library or the GPU is missing.
 from __future__ import annotations
 
 import ctypes
+from typing import NamedTuple
 
 import numpy as np
 
@@ -2035,3 +2036,124 @@ def radial_sum_array(image) -> np.ndarray:
     with _lib.lock():
         _lib.call("pmi_radial_sum", _lib.ptr(image), RADIAL_TYPES[image.dtype], n, _lib.ptr(out))
     return out
+
+
+# ---- image blur (csrc/blur.hip): the "smooth" and "convolve" renders ---------------------------------------------------------
+class BlurPlan(NamedTuple):
+    """What ``render._fftconvolve`` does to an image of one shape, decided on the host (``blur_plan``)."""
+    route: str                  # "spatial": scipy.ndimage.gaussian_filter in bits; "direct": the sum in place of the FFT
+    kernel: tuple               # (kernel_height, kernel_width) of the reference
+    radius: tuple               # (r_y, r_x)
+    weights: tuple              # (w_y, w_x): float64 vectors of 2 r + 1 values, None for a skipped axis
+    skip: tuple                 # (skip_y, skip_x)
+    S: float                    # the reference's kernel.sum() on the direct route (1.0 on the spatial one)
+
+
+def gaussian_kernel1d(sigma: float, radius: int) -> np.ndarray:
+    """scipy.ndimage's ``_gaussian_kernel1d(sigma, 0, radius)``: normalised float64 weights, symmetric.  The expressions
+    are scipy's, so a NumPy scalar sigma is promoted as scipy promotes it."""
+    sigma2 = sigma * sigma
+    x = np.arange(-radius, radius + 1)
+    phi_x = np.exp(-0.5 / sigma2 * x ** 2)
+    return phi_x / phi_x.sum()
+
+
+def spatial_plan(blur_width, blur_height, kernel=(0, 0)) -> BlurPlan:
+    """``gaussian_filter(sigma=(blur_height, blur_width), mode="constant", truncate=5.0)`` as scipy runs it: an axis with
+    a sigma ``<= 1e-15`` is skipped, the radius is ``int(5.0 * float(sigma) + 0.5)``, the weights ``gaussian_kernel1d`` of
+    the sigma as it was given: scipy squares a float32 sigma (``_render_convolve`` makes one from the float32 median)
+    in float32."""
+    radius, weights, skip = [], [], []
+    for sigma in (blur_height, blur_width):
+        if sigma > 1e-15:
+            sd = float(sigma)
+            lw = int(5.0 * sd + 0.5)
+            radius.append(lw), weights.append(gaussian_kernel1d(sigma, lw)), skip.append(False)
+        else:
+            radius.append(0), weights.append(None), skip.append(True)
+    return BlurPlan("spatial", tuple(kernel), tuple(radius), tuple(weights), tuple(skip), 1.0)
+
+
+def direct_plan(kernel_width: int, kernel_height: int, blur_width, blur_height) -> BlurPlan:
+    """The reference's kernel of its FFT route: ``signal.windows.gaussian(kernel, width)`` per axis (not normalised) and
+    ``S = np.outer(kernel_y, kernel_x).sum()``; no axis is skipped."""
+    from scipy import signal
+    with np.errstate(all="ignore"):
+        kernel_y = np.asarray(signal.windows.gaussian(kernel_height, blur_height), np.float64)
+        kernel_x = np.asarray(signal.windows.gaussian(kernel_width, blur_width), np.float64)
+        S = float(np.outer(kernel_y, kernel_x).sum())
+    return BlurPlan("direct", (kernel_height, kernel_width), (kernel_height // 2, kernel_width // 2), (kernel_y, kernel_x),
+                    (False, False), S)
+
+
+def blur_plan(n_y: int, n_x: int, blur_width, blur_height) -> BlurPlan:
+    """The route of picasso/render.py:1433-1460 for an ``n_y`` x ``n_x`` image and what each axis is blurred with
+    (``spatial_plan`` or ``direct_plan``).  A NaN width raises ValueError and an infinite one OverflowError from
+    ``int(np.round(...))``, as in the reference."""
+    kernel_width = 10 * int(np.round(blur_width)) + 1
+    kernel_height = 10 * int(np.round(blur_height)) + 1
+    spatial = (
+        kernel_height < 0.05 * n_y
+        and kernel_width < 0.05 * n_x
+        and max(kernel_height, kernel_width) <= 101
+    )
+    if spatial:
+        return spatial_plan(blur_width, blur_height, (kernel_height, kernel_width))
+    return direct_plan(kernel_width, kernel_height, blur_width, blur_height)
+
+
+def _blur_args(plan: BlurPlan):
+    """The tail of the C calls: weights, radii, mode, scale; and the arrays to keep alive."""
+    w_y, w_x = (None if w is None else np.ascontiguousarray(w, np.float64) for w in plan.weights)
+    with np.errstate(all="ignore"):
+        scale = float(np.float64(1.0) / np.float64(plan.S))
+    return (_lib.ptr(w_y), int(plan.radius[0]), _lib.ptr(w_x), int(plan.radius[1]), 1 if plan.route == "spatial" else 0, scale), (w_y, w_x)
+
+
+def blur_with_plan(image, plan: BlurPlan) -> np.ndarray:
+    """The separable blur of csrc/blur.hip on a float32 image with the weights of ``plan`` -> float32 image."""
+    image = np.asarray(image)
+    if image.ndim != 2 or image.dtype != np.float32:
+        raise TypeError(f"a 2-D float32 image is needed, not {image.dtype} with {image.ndim} dimensions")
+    image = np.ascontiguousarray(image)
+    _lib.require_gpu()
+    out = np.empty_like(image)
+    tail, keep = _blur_args(plan)
+    with _lib.lock():
+        _lib.call("pmi_blur", _lib.ptr(image), _lib.ptr(out), image.shape[0], image.shape[1], *tail)
+    return out
+
+
+def blur_array(image, blur_width, blur_height) -> np.ndarray:
+    """``render._fftconvolve`` of a float32 image on the device -> float32 image (``blur_plan`` says how)."""
+    shape = np.shape(image)
+    if len(shape) != 2:
+        raise TypeError(f"a 2-D float32 image is needed, not {len(shape)} dimensions")
+    return blur_with_plan(image, blur_plan(shape[0], shape[1], blur_width, blur_height))
+
+
+def render_dims(oversampling, y_min, x_min, y_max, x_max):
+    """(n_y, n_x) of a render (render.py:224-225); needs no GPU."""
+    ny, nx = ctypes.c_int64(), ctypes.c_int64()
+    _lib.call("pmi_render_dims", float(oversampling), float(y_min), float(x_min), float(y_max), float(x_max),
+              ctypes.byref(ny), ctypes.byref(nx))
+    if ny.value <= 0 or nx.value <= 0:
+        raise ValueError("empty viewport")
+    return int(ny.value), int(nx.value)
+
+
+def render_blurred_arrays(x, y, oversampling, y_min, x_min, y_max, x_max, blur_width, blur_height):
+    """-> (n, image float32): the histogram render followed by ``_fftconvolve(image, blur_width, blur_height)`` in one
+    call; the histogram never leaves the device."""
+    n_y, n_x = render_dims(oversampling, y_min, x_min, y_max, x_max)
+    plan = blur_plan(n_y, n_x, blur_width, blur_height)
+    _lib.require_gpu()
+    x = np.ascontiguousarray(x, np.float32)
+    y = np.ascontiguousarray(y, np.float32)
+    image = np.empty((n_y, n_x), np.float32)
+    n = ctypes.c_int64(0)
+    tail, keep = _blur_args(plan)
+    with _lib.lock():
+        _lib.call("pmi_render_blurred", _lib.ptr(x), _lib.ptr(y), len(x), float(oversampling), float(y_min), float(x_min),
+                  float(y_max), float(x_max), *tail, _lib.ptr(image), n_y, n_x, ctypes.byref(n))
+    return int(n.value), image

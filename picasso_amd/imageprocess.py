@@ -1,5 +1,6 @@
 """picasso.imageprocess surface for RCC drift correction (picasso/imageprocess.py:27-217):
-``xcorr``, ``get_image_shift``, ``rcc``.  The correlations, the centre crop, the peak search, the fit window
+``xcorr``, ``get_image_shift``, ``rcc``, and ``find_fiducials`` (:220-280) on top of the one-pixel-blur render
+(csrc/blur.hip), the device's local maxima and its circular picks.  The correlations, the centre crop, the peak search, the fit window
 (csrc/xcorr.hip, hipFFT, float64) and the bounded Gaussian fit of the window — the reference's scipy
 ``curve_fit`` call, restated as a Trust Region Reflective solver with one thread per pair (csrc/peakfit.hip) —
 all run on the device.
@@ -55,6 +56,32 @@ def rcc(segments, max_shift: float | None = None, callback=None):
             if callback is not None:
                 callback(flag)
     return lib.minimize_shifts(shifts_x, shifts_y)
+
+
+def find_fiducials(locs: pd.DataFrame, info: list[dict]) -> tuple[list[tuple[int, int]], int]:
+    """Pick centres of regions dense enough to be fiducial markers (imageprocess.py:220-280) -> (picks, box).  The
+    one-pixel-blur render at oversampling 1 over the whole frame and the local maxima above its 99th percentile (taken
+    on the host) run on the device; so do the members of the circular picks of radius ``box / 2``, of which only the
+    counts are used: no per-pick frame is built.  A pick is kept when it holds more than ``0.8 * Frames`` rows."""
+    from . import localize, postprocess, render
+    lib.get_from_metadata(info, "Pixelsize", raise_error=True)          # render.render refuses a missing Pixelsize
+    (y_min, x_min), (y_max, x_max) = render._viewport(info, None)
+    image = render._render_smooth(locs, 1.0, y_min, x_min, y_max, x_max)[1]
+    threshold = np.percentile(image.flatten(), 99)
+    # box size should be an odd number, corresponding to approximately 900 nm
+    pixelsize = lib.get_from_metadata(info, "Pixelsize", default=130)
+    box = int(np.round(900 / pixelsize))
+    box = box + 1 if box % 2 == 0 else box
+    y, x, _ = localize.identify_in_image(image, threshold, box=box)
+    picks = [(xi, yi) for xi, yi in zip(x, y)]
+    n_frames = lib.get_from_metadata(info, "Frames", default=0)
+    min_n = 0.8 * n_frames
+    if len(picks) == 0:
+        return picks, box
+    _, offsets, _ = postprocess._circle_members(locs, info, picks, box / 2)
+    counts = np.diff(offsets)
+    picks = [pick for i, pick in enumerate(picks) if counts[i] > min_n]
+    return picks, box
 
 
 def radial_sum(image):

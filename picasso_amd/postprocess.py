@@ -15,6 +15,7 @@ from them (:2964-3156 ``undrift_from_fiducials``, ``undrift_from_picked``) on to
 from __future__ import annotations
 
 import math
+from copy import deepcopy
 import warnings
 from collections import OrderedDict
 from typing import Callable, Literal
@@ -1078,7 +1079,7 @@ def undrift_from_fiducials(locs: pd.DataFrame, info: list[dict], picks: list[tup
     locs = locs.copy()
     pixelsize = lib.get_from_metadata(info, "Pixelsize", raise_error=True)
     if picks is None:
-        raise NotImplementedError("picks=None: find_fiducials needs the 'smooth' render, which has no kernel; pass the picks")
+        raise NotImplementedError("picks=None is not routed here: call imageprocess.find_fiducials and pass its picks and box / 2")
     if pick_size is None:
         raise ValueError("pick_size (radius in camera pixels) must be provided when picks are given as a list of "
                          "coordinates.")
@@ -1099,6 +1100,70 @@ def undrift_from_fiducials(locs: pd.DataFrame, info: list[dict], picks: list[tup
     new_info = info + [{"Generated by": f"Picasso v{__version__} Undrift from picked", "Number of picks": len(picks),
                         "Pick radius (nm)": pick_radius * pixelsize}]
     return locs, new_info, drift
+
+
+# ---- channel alignment (postprocess.py:3296-3443) ------------------------------------------------------------------
+# Not rebound by localize.install().  Host compositions over the one-pixel-blur render (csrc/blur.hip) and the RCC.
+ALIGN_NAMES = ("align", "align_rcc")
+
+
+def align(locs: list[pd.DataFrame], infos: list[dict], display: bool = False, *, apply_shifts: bool = True,
+          return_shifts: bool = False) -> pd.DataFrame:
+    """Align the channels in ``locs`` by the RCC shifts between their rendered images (postprocess.py:3296-3349): one
+    ``"smooth"`` render per channel at oversampling 1 over the whole frame, ``imageprocess.rcc`` over the images, and,
+    when ``apply_shifts``, ``x`` and ``y`` of each of the caller's tables shifted in place.  ``return_shifts`` adds
+    ``(shift_x, shift_y)``.  ``display`` is not used.  A channel without ``Pixelsize`` raises KeyError as in the
+    reference's ``render.render``."""
+    images = []
+    for locs_, info_ in zip(locs, infos):
+        lib.get_from_metadata(info_, "Pixelsize", raise_error=True)
+        (y_min, x_min), (y_max, x_max) = render._viewport(info_, None)
+        _, image = render._render_smooth(locs_, 1.0, y_min, x_min, y_max, x_max)
+        images.append(image)
+    shift_y, shift_x = imageprocess.rcc(images, callback=lambda _: None)
+    if apply_shifts:
+        for i, (locs_, dx, dy) in enumerate(zip(locs, shift_x, shift_y)):
+            locs_["y"] -= dy
+            locs_["x"] -= dx
+    if return_shifts:
+        shifts = (shift_x, shift_y)
+        return locs, shifts
+    else:
+        return locs
+
+
+def align_rcc(locs: list[pd.DataFrame], infos: list[list[dict]], display: bool = False,
+              return_shifts: bool = False) -> pd.DataFrame:
+    """``align`` repeated on a deep copy until every channel's ``|dx| + |dy|`` is at most 0.001 px, five times at the
+    most (postprocess.py:3352-3443).  ``return_shifts`` adds one ``(mean dx, mean dy)`` pair per iteration.  ``align``
+    returns two shift arrays, so the reference's ``z`` branch is never taken and ``z`` stays as it is.  ``display`` is
+    ignored."""
+    locs = deepcopy(locs)
+    max_iterations = 5
+    convergence = 0.001  # (camera pixels), around 0.1 nm
+    shift_x = []
+    shift_y = []
+    for iteration in range(max_iterations):
+        completed = True
+        shift = align(locs, infos, display=False, apply_shifts=False, return_shifts=True)[1]
+        temp_shift_x = []
+        temp_shift_y = []
+        for i, locs_ in enumerate(locs):
+            if np.absolute(shift[0][i]) + np.absolute(shift[1][i]) > convergence:
+                completed = False
+            locs_["x"] -= shift[0][i]
+            locs_["y"] -= shift[1][i]
+            temp_shift_x.append(shift[0][i])
+            temp_shift_y.append(shift[1][i])
+        shift_x.append(np.mean(temp_shift_x))
+        shift_y.append(np.mean(temp_shift_y))
+        if completed:
+            break
+    if return_shifts:
+        shifts = list(zip(shift_x, shift_y))
+        return locs, shifts
+    else:
+        return locs
 
 
 # ---- pick similar (postprocess.py:476-736, :820-957) -------------------------------------------------------------

@@ -1,8 +1,10 @@
-"""picasso.render surface for the two render modes on the drift-correction / display path:
+"""picasso.render surface for the render modes on the drift-correction / display path:
 ``blur_method=None`` (2-D histogram), ``"gaussian"`` (one separable Gaussian per localization,
 widths = localization precisions) and ``"gaussian_iso"`` (one width, their mean).  picasso/render.py:37-175 ``render``,
 :798-853 ``_render_hist``, :1020-1070 ``_render_gaussian``; the pixels are computed by
-csrc/render.hip.  Rotated views (``ang``) and the other blur methods are not built; they
+csrc/render.hip.  The two blurred histograms, ``_render_smooth`` (:1349-1410) and ``_render_convolve`` (:1249-1319)
+with ``_fftconvolve`` (:1413-1460) under them, are computed by csrc/blur.hip and called by name: ``render()`` still
+refuses ``blur_method="smooth"`` / ``"convolve"``.  Rotated views (``ang``) are not built; they
 raise instead of falling back to a CPU path.
 
 Zero blur width.  The reference draws each localization in ``_draw_gaussian_loc``, compiled by numba
@@ -57,7 +59,8 @@ def render(locs: pd.DataFrame, info, oversampling: float = 1.0, viewport=None, b
     if blur_method == "gaussian_iso":
         return _render_gaussian_iso(locs, oversampling, y_min, x_min, y_max, x_max, min_blur_width)
     if blur_method in _NOT_BUILT:
-        raise NotImplementedError(f"blur_method={blur_method!r} has no HIP kernel in picasso_amd; there is no CPU fallback")
+        raise NotImplementedError(f"blur_method={blur_method!r} is not routed through render(): call "
+                                  f"render._render_{blur_method} (csrc/blur.hip); there is no CPU fallback")
     raise Exception("blur_method not understood.")
 
 
@@ -119,6 +122,46 @@ def _render_gaussian_iso(locs, oversampling, y_min, x_min, y_max, x_max, min_blu
                                  min_blur_width=min_blur_width, iso=True)
 
 
+def _refuse_ang(ang) -> None:
+    if ang is not None:
+        raise NotImplementedError("rotated rendering (ang) has no HIP kernel in picasso_amd")
+
+
+def _fftconvolve(image: lib.FloatArray2D, blur_width: float, blur_height: float) -> lib.FloatArray2D:
+    """picasso/render.py:1413-1460 on the device (csrc/blur.hip): scipy's ``gaussian_filter`` in every bit where the
+    reference takes it, a float64 direct sum where the reference takes the single-precision FFT."""
+    return backend.blur_array(image, blur_width, blur_height)
+
+
+def _render_smooth(locs: pd.DataFrame, oversampling: float, y_min: float, x_min: float, y_max: float, x_max: float,
+                   ang: tuple[float, float, float] | Rotation | None = None) -> tuple[int, lib.FloatArray2D]:
+    """picasso/render.py:1349-1410: the histogram blurred by one display pixel; fill and blur in one device call."""
+    _refuse_ang(ang)
+    return backend.render_blurred_arrays(locs["x"].to_numpy(), locs["y"].to_numpy(), oversampling, y_min, x_min, y_max,
+                                         x_max, 1, 1)
+
+
+def _render_convolve(locs: pd.DataFrame, oversampling: float, y_min: float, x_min: float, y_max: float, x_max: float,
+                     min_blur_width: float, ang: tuple[float, float, float] | Rotation | None = None) -> tuple[int, lib.FloatArray2D]:
+    """picasso/render.py:1249-1319: the histogram blurred by the median localization precision of the rows in view
+    (the host takes the two medians); fill and blur in one device call."""
+    _refuse_ang(ang)
+    x, y = locs["x"].to_numpy(), locs["y"].to_numpy()
+    with np.errstate(invalid="ignore"):          # strict on all four sides, float32 columns compared as float64 (_render_setup)
+        xd, yd = np.asarray(x, np.float32).astype(np.float64), np.asarray(y, np.float32).astype(np.float64)
+        in_view = (xd > x_min) & (yd > y_min) & (xd < x_max) & (yd < y_max)
+    n = int(in_view.sum())
+    if n == 0:
+        return 0, np.zeros(backend.render_dims(oversampling, y_min, x_min, y_max, x_max), dtype=np.float32)
+    blur_width = oversampling * max(
+        np.median(locs["lpx"].to_numpy()[in_view]), min_blur_width
+    )
+    blur_height = oversampling * max(
+        np.median(locs["lpy"].to_numpy()[in_view]), min_blur_width
+    )
+    return backend.render_blurred_arrays(x, y, oversampling, y_min, x_min, y_max, x_max, blur_width, blur_height)
+
+
 def _older_name(name: str) -> None:
     lib.deprecation_warning(f"Deprecation warning: the '{name}' function is deprecated and will be removed in "
                             f"v0.11.0. Use _{name} instead if necessary.")
@@ -141,3 +184,17 @@ def render_gaussian_iso(locs, oversampling, y_min, x_min, y_max, x_max, min_blur
     """Older public name of ``_render_gaussian_iso`` (picasso/render.py:1118-1145)."""
     _older_name("render_gaussian_iso")
     return _render_gaussian_iso(locs, oversampling, y_min, x_min, y_max, x_max, min_blur_width, ang=ang)
+
+
+def render_convolve(locs: pd.DataFrame, oversampling: float, y_min: float, x_min: float, y_max: float, x_max: float,
+                    min_blur_width: float, ang: tuple[float, float, float] | Rotation | None = None) -> tuple[int, lib.FloatArray2D]:
+    """Older public name of ``_render_convolve`` (picasso/render.py:1219-1246)."""
+    _older_name("render_convolve")
+    return _render_convolve(locs, oversampling, y_min, x_min, y_max, x_max, min_blur_width, ang=ang)
+
+
+def render_smooth(locs: pd.DataFrame, oversampling: float, y_min: float, x_min: float, y_max: float, x_max: float,
+                  ang: tuple[float, float, float] | Rotation | None = None) -> tuple[int, lib.FloatArray2D]:
+    """Older public name of ``_render_smooth`` (picasso/render.py:1322-1346)."""
+    _older_name("render_smooth")
+    return _render_smooth(locs, oversampling, y_min, x_min, y_max, x_max, ang=ang)
