@@ -60,6 +60,8 @@
  *                      threshold_otsu)
  *   pmi_average_*      picasso/average.py:49-118 align_group_core, :354-530 average (the average image of
  *                      picasso/render.py:739-773 render_hist_numba, the rotation and shift search, the transform)
+ *   pmi_cumexp_fit*    picasso/lib.py:1263-1327 cumulative_exponential, fit_cum_exp, estimate_kinetic_rate, under
+ *                      picasso/postprocess.py:1634-1917 evaluate_picks, pick_kinetics, pick_properties
  *   pmi_kinetics_*     picasso/postprocess.py:1985-2004 _dark_times (:1920-1982 compute_dark_times,
  *                      dark_times), :3580-3649 groupprops
  *   pmi_pairs_*        picasso/postprocess.py:37-94 get_index_blocks, :169-204
@@ -727,6 +729,30 @@ int pmi_kinetics_dark_search_dev(const int64_t *d_frame, const int32_t *d_rows, 
                                  int64_t *d_dark, void *stream);
 int pmi_kinetics_stats_dev(const int32_t *d_rows, const int32_t *d_start, int64_t n, int64_t n_groups,
                            const pmi_kinetics_column *columns, int n_columns, void *stream);
+
+/* ---- kinetic rates of picks (picasso/lib.py:1263-1327 estimate_kinetic_rate, fit_cum_exp; csrc/cumexp.hip,
+ * csrc/cumexp_core.h) ------------------------------------------------------------------------------------------- *
+ * The samples of n_seg segments as a CSR: float64 `values` (n_values of them, below 2^31 - 1) and int64
+ * `offsets[n_seg + 1]` ascending from 0 to at most n_values (checked; PMI_ERR_ARG otherwise).  `kind` names the column
+ * the values were converted from: 0 an integer column (exact in float64 below 2^53), 1 float32, 2 float64.  Per
+ * segment of n samples, as lib.estimate_kinetic_rate decides:
+ *   n <= 2, or max - min == 0    t = np.nanmean of the samples in the column's arithmetic (kind 0: the exact float64 sum
+ *                                over n; kinds 1, 2: NumPy's add.reduce with NaN as 0 in float32 / float64 over the count
+ *                                of the values that are not NaN); NaN for no sample; a, c, cost NaN; 0 iterations
+ *   otherwise                    the samples in ascending order x, y = 1 .. n, and the bounded least-squares fit of
+ *                                a (1 - exp(-x / t)) + c in float64 from p0 = (n, mean, min) with a in [0, inf),
+ *                                t in [min, max], c in [0, inf): a damped Newton method (cumexp_core.h) that only ever
+ *                                accepts a point whose cost is not above the last one, and ends on its own tolerances
+ * d_fit holds 4 x n_seg float64: a, t, c and the final cost 0.5 sum r^2, one array behind the other; d_info 2 x n_seg
+ * int32: the passes over the samples, then the status: 0 converged (or not fitted), 1 the iteration cap (300 passes),
+ * 2 an input scipy refuses with ValueError (a NaN or an infinity in a segment that would be fitted, or a negative
+ * minimum); with status 2 the four values are NaN.  Bit parity with scipy's trust-region solver is not claimed: the
+ * contract is a cost that is not above scipy's (tests/test_gpu_pickkin.py).  One wavefront per segment, no atomics;
+ * scratch from the library's arena; runs on `stream` and synchronises it.  pmi_cumexp_fit is the same from host arrays. */
+int pmi_cumexp_fit_dev(const double *d_values, int64_t n_values, const int64_t *d_offsets, int64_t n_seg, int kind,
+                       double *d_fit, int32_t *d_info, void *stream);
+int pmi_cumexp_fit(const double *values, int64_t n_values, const int64_t *offsets, int64_t n_seg, int kind, double *fit,
+                   int32_t *info);
 
 /* ---- nearest-neighbour distances (picasso/postprocess.py:3704-3739 nn_analysis, picasso/spinna.py:696-747 get_NN_dist,
  * csrc/knn.hip, csrc/knn_search.h) ------------------------------------------------------------------------------- *

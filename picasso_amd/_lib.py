@@ -95,6 +95,8 @@ SYMBOLS = {
     "pmi_blur_dev": (_i32, [_p, _p, _i64, _i64, _p, _i64, _p, _i64, _i32, _f64, _p]),
     "pmi_blur": (_i32, [_p, _p, _i64, _i64, _p, _i64, _p, _i64, _i32, _f64]),
     "pmi_render_blurred": (_i32, [_p, _p, _i64, _f64, _f64, _f64, _f64, _f64, _p, _i64, _p, _i64, _i32, _f64, _p, _i64, _i64, _p]),
+    "pmi_cumexp_fit_dev": (_i32, [_p, _i64, _p, _i64, _i32, _p, _p, _p]),
+    "pmi_cumexp_fit": (_i32, [_p, _i64, _p, _i64, _i32, _p, _p]),
     "pmi_xcorr": (_i32, [_p, _p, _i64, _i64, _p]),
     "pmi_rcc_pairs": (_i32, [_p, _i64, _i64, _i64, _i64, _i32, _p, _p, _p, _p]),
     "pmi_rcc_pair_list": (_i32, [_p, _i64, _i64, _i64, _i64, _i32, _p, _i64, _p, _p, _p, _p]),

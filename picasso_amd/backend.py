@@ -2157,3 +2157,56 @@ def render_blurred_arrays(x, y, oversampling, y_min, x_min, y_max, x_max, blur_w
         _lib.call("pmi_render_blurred", _lib.ptr(x), _lib.ptr(y), len(x), float(oversampling), float(y_min), float(x_min),
                   float(y_max), float(x_max), *tail, _lib.ptr(image), n_y, n_x, ctypes.byref(n))
     return int(n.value), image
+
+
+# ---- kinetic rates of picks (csrc/cumexp.hip, picasso/lib.py:1263-1327) -----------------------------------------------------
+CUMEXP_CONVERGED, CUMEXP_ITER_CAP, CUMEXP_REFUSED = 0, 1, 2      # the status codes of pmi_cumexp_fit
+
+
+class KineticRates(NamedTuple):
+    """Per segment: the fit's ``a``, ``t``, ``c`` and final cost ``0.5 * sum(r ** 2)`` (float64; ``t`` is the kinetic rate,
+    and the mean of a segment the reference does not fit, whose ``a``, ``c`` and ``cost`` are NaN), the passes over the
+    samples and the status (int32: CUMEXP_CONVERGED, CUMEXP_ITER_CAP, CUMEXP_REFUSED)."""
+    a: np.ndarray
+    t: np.ndarray
+    c: np.ndarray
+    cost: np.ndarray
+    iterations: np.ndarray
+    status: np.ndarray
+
+
+def cumexp_kind(dtype) -> int:
+    """The column kind pmi_cumexp_fit takes: 0 an integer (or bool) column, 1 float32, 2 float64."""
+    dtype = np.dtype(dtype)
+    if dtype.kind in "iub":
+        return 0
+    if dtype == np.float32:
+        return 1
+    if dtype == np.float64:
+        return 2
+    raise TypeError(f"no kinetic rate of a {dtype} column")
+
+
+def kinetic_rates(values, offsets) -> KineticRates:
+    """``lib.estimate_kinetic_rate`` of every segment ``values[offsets[s]:offsets[s + 1]]`` in one device call
+    (pmi_cumexp_fit): the mean of a segment of at most two samples or of equal samples, the ``t`` of the bounded
+    cumulative-exponential fit otherwise.  ``values`` is one column (integer, float32 or float64; integers must stay
+    below 2**53), ``offsets`` the S + 1 ascending offsets from 0.  The values are not changed."""
+    _lib.require_gpu()
+    values = np.asarray(values)
+    if values.ndim != 1:
+        raise ValueError(f"values must be one column, not an array of shape {values.shape}")
+    kind = cumexp_kind(values.dtype)
+    offsets = np.ascontiguousarray(_index_column(offsets, "offsets"))
+    if offsets.ndim != 1 or len(offsets) < 1 or offsets[0] != 0 or (np.diff(offsets) < 0).any() or offsets[-1] > len(values):
+        raise ValueError("offsets must be the S + 1 ascending offsets of the segments, from 0 to at most len(values)")
+    if kind == 0 and len(values) and max(int(values.max()), -int(values.min())) >= 2 ** 53:
+        raise ValueError("integer samples must stay below 2**53")
+    S = len(offsets) - 1
+    as_f64 = np.ascontiguousarray(values, np.float64)
+    fit = np.full((4, S), np.nan, np.float64)
+    info = np.zeros((2, S), np.int32)
+    if S:
+        with _lib.lock():
+            _lib.call("pmi_cumexp_fit", _lib.ptr(as_f64), len(as_f64), _lib.ptr(offsets), S, kind, _lib.ptr(fit), _lib.ptr(info))
+    return KineticRates(fit[0], fit[1], fit[2], fit[3], info[0], info[1])

@@ -159,3 +159,49 @@ def get_pick_rectangle_corners(start_x: float, start_y: float, end_x: float, end
     xs = [start_x - across_x, start_x + across_x, end_x + across_x, end_x - across_x]
     ys = [start_y + across_y, start_y - across_y, end_y - across_y, end_y + across_y]
     return [float(v) for v in xs], [float(v) for v in ys]
+
+
+# ---- kinetic rates (picasso/lib.py:1263-1327) on top of csrc/cumexp.hip --------------------------------------------
+KINETICS_NAMES = ("cumulative_exponential", "fit_cum_exp", "estimate_kinetic_rate")
+
+
+def cumulative_exponential(x: FloatArray1D, a: float, t: float, c: float) -> FloatArray1D:
+    """Used for binding kinetics estimation (picasso/lib.py:1263-1270)."""
+    return a * (1 - np.exp(-(x / t))) + c
+
+
+def _one_segment(data):
+    """One segment through the kernel -> the backend's KineticRates with one entry each.  A fit that ends on the
+    iteration cap raises RuntimeError, as scipy's does; an input scipy refuses raises ValueError."""
+    from . import backend
+    data = np.asarray(data)
+    rates = backend.kinetic_rates(data, [0, len(data)])
+    if rates.status[0] == backend.CUMEXP_REFUSED:
+        raise ValueError("the samples of a fit must be finite and must not be negative")
+    if rates.status[0] == backend.CUMEXP_ITER_CAP:
+        raise RuntimeError("Optimal parameters not found: the fit reached its iteration cap")
+    return rates
+
+
+def fit_cum_exp(data: FloatArray1D) -> dict:
+    """Fit a cumulative exponential function to data (picasso/lib.py:1273-1302): sorts ``data`` IN PLACE, as the
+    reference does, and returns ``best_values`` (a, t, c), ``data`` and ``best_fit``.  The fit is the device's
+    (csrc/cumexp.hip): a bounded descent from the reference's p0 to a cost that is not above scipy's; not scipy's bits."""
+    rates = _one_segment(data)
+    data.sort()
+    if rates.a[0] != rates.a[0]:
+        raise ValueError("fit_cum_exp needs more than two samples that are not all equal")
+    popt = (float(rates.a[0]), float(rates.t[0]), float(rates.c[0]))
+    return {"best_values": {"a": popt[0], "t": popt[1], "c": popt[2]}, "data": data,
+            "best_fit": cumulative_exponential(data, *popt)}
+
+
+def estimate_kinetic_rate(data: FloatArray1D) -> float:
+    """Mean dark / bright time from the cumulative-exponential fit (picasso/lib.py:1305-1327): the mean of at most two or
+    of equal samples, the fitted ``t`` otherwise; one segment through the kernel that ``postprocess.pick_kinetics`` runs
+    over all picks.  A fitted ``data`` is sorted IN PLACE, as the reference's is."""
+    rates = _one_segment(data)
+    if rates.a[0] == rates.a[0]:
+        data.sort()
+    rate = rates.t[0]
+    return np.float32(rate) if np.asarray(data).dtype == np.float32 and rates.a[0] != rates.a[0] else np.float64(rate)

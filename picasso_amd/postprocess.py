@@ -1238,3 +1238,236 @@ def pick_similar(locs: pd.DataFrame, info: list[dict], picks: list[tuple], d: fl
     x_similar = np.concatenate([x_similar.astype(np.float64), cx[candidates][keep]])
     y_similar = np.concatenate([y_similar.astype(np.float64), cy[candidates][keep]])
     return list(zip(x_similar, y_similar))
+
+
+# ---- pick kinetics (postprocess.py:1634-1917) on top of csrc/cumexp.hip ---------------------------------------------
+# Not rebound by localize.install(), like the picks they are built on.
+KINETIC_PICK_NAMES = ("evaluate_picks", "_pick_kinetics_single", "pick_kinetics", "pick_properties")
+_LINK_ALL = 999999                  # the reference's r_max inside a pick: every localization of the pick may link
+
+
+def _pick_columns(picked_locs: list[pd.DataFrame]) -> list:
+    """The columns all picks share.  The reference decides per pick whether it links; here the picks are one table."""
+    columns = list(picked_locs[0].columns)
+    if any(list(locs.columns) != columns for locs in picked_locs):
+        raise ValueError("all picks must have the same columns")
+    return columns
+
+
+def _link_picks(picks: list[pd.DataFrame], ids: np.ndarray, info, max_dark_time):
+    """``link(pick, info, r_max=999999, max_dark_time=max_dark_time)`` of every non-empty pick in one device pass ->
+    (binding events, pick-major and in the reference's order inside a pick; the pick of every event).
+
+    Each pick is sorted by frame with the reference's own pandas call.  The picks then become one table sorted by frame:
+    pick k's frames are moved by k strides, a stride being wider than the span of all frames plus the dark time, so no
+    window of the link reaches another pick, the link groups come out numbered pick by pick, and the ``group`` column
+    (zeros without one) keeps separating rows inside a pick, as it does in the reference.  The combination reads the
+    frames as they are.  One reference quirk needs the end of a table: a row that shares the pick's last frame with a
+    later row scans the LAST row of the table (csrc/link.hip).  Picks whose last frame holds several localizations are
+    therefore linked in a call of their own."""
+    ordered = [locs.sort_values(kind="quicksort", by="frame") for locs in picks]
+    frames = [locs["frame"].to_numpy() for locs in ordered]
+    alone = np.array([len(f) > 1 and f[-2] == f[-1] for f in frames], bool)
+    tables, table_ids = [], []
+    batch = [k for k in range(len(picks)) if not alone[k]]
+    if batch:
+        cat = pd.concat([ordered[k] for k in batch])
+        sizes = np.array([len(frames[k]) for k in batch])
+        rank = np.repeat(np.arange(len(batch), dtype=np.int64), sizes)
+        frame = _frame_numbers(cat["frame"].to_numpy(), "frame")
+        step = math.floor(max_dark_time + 1)
+        stride = int(frame.max()) - int(frame.min()) + max(int(step), 0) + 2
+        if stride * len(batch) >= backend.KINETICS_FRAME_LIMIT:
+            raise ValueError("the frames of the picks span too much to be linked in one pass")
+        moved = frame - int(frame.min()) + rank * stride
+        group = cat["group"].to_numpy() if "group" in cat.columns else np.zeros(len(cat), dtype=np.int32)
+        d_link_group, n_groups = _device_link_groups(moved, cat["x"].to_numpy(), cat["y"].to_numpy(), _LINK_ALL,
+                                                     max_dark_time, group)
+        pick_of_group = np.zeros(max(n_groups, 1), np.int64)
+        pick_of_group[d_link_group.cpu().numpy()] = np.asarray(ids)[batch][rank]
+        linked = _combine(cat, info, d_link_group, n_groups, True)
+        tables.append(linked), table_ids.append(pick_of_group[linked.index.to_numpy()])
+    for k in np.flatnonzero(alone):
+        linked = link(picks[k], info, r_max=_LINK_ALL, max_dark_time=max_dark_time)
+        tables.append(linked), table_ids.append(np.full(len(linked), ids[k], np.int64))
+    events, event_ids = pd.concat(tables, ignore_index=True), np.concatenate(table_ids)
+    order = np.argsort(event_ids, kind="stable")
+    return events.iloc[order].reset_index(drop=True), event_ids[order]
+
+
+def _pick_events(picked_locs: list[pd.DataFrame], info, max_dark_time):
+    """What the reference's loop has after ``compute_dark_times`` for every pick, as one pick-major table -> (events,
+    the pick of every event, events per pick before the dark-time filter)."""
+    n_picks = len(picked_locs)
+    sizes = np.array([len(locs) for locs in picked_locs], np.int64)
+    filled = np.flatnonzero(sizes)
+    columns = _pick_columns(picked_locs)
+    picks = [picked_locs[k] for k in filled]
+    if not picks:
+        return None, np.zeros(0, np.int64), np.zeros(n_picks, np.int64)
+    if "len" not in columns:
+        events, ids = _link_picks(picks, filled, info, max_dark_time)
+    else:
+        events, ids = pd.concat(picks, ignore_index=True), np.repeat(filled, sizes[filled])
+    linked_sizes = np.bincount(ids, minlength=n_picks)
+    if len(events) == 0:
+        return events, ids, linked_sizes
+    # dark times: one search over all picks, a (pick, group) pair as the label
+    frame, lens = events["frame"].to_numpy(), events["len"].to_numpy()
+    with np.errstate(over="ignore"):
+        last_frame = frame + lens - 1
+    labels = ids
+    if "group" in events.columns:
+        group = _group_labels(events["group"].to_numpy())
+        span = int(group.max()) - int(group.min()) + 1
+        if span * n_picks >= 2 ** 62:
+            raise ValueError("the group labels span too much to be paired with the picks")
+        labels = ids * span + (group - int(group.min()))
+    f = _frame_numbers(frame, "frame")
+    dark = backend.DarkTable(f, labels, _frame_numbers(last_frame, "last_frame")).search()
+    # the reference keeps a dark time below ITS table's largest frame: the pick's, not that of all picks
+    starts = np.flatnonzero(np.r_[True, ids[1:] != ids[:-1]])
+    pick_max = np.repeat(np.maximum.reduceat(f, starts), np.diff(np.r_[starts, len(ids)]))
+    dark[dark >= pick_max] = -1
+    events["dark"] = np.int32(dark)
+    keep = (events["dark"] != -1).to_numpy()
+    return events[keep].reset_index(drop=True), ids[keep], linked_sizes
+
+
+def _pick_rates(events: pd.DataFrame, ids: np.ndarray, n_picks: int):
+    """The two ``kinetic_rates`` calls over all picks, and the reference's in-place sort: ``fit_cum_exp`` sorts the array
+    it is handed, ``Series.to_numpy()`` hands it a view of the table (pandas 2.3.3 without copy-on-write, recorded in
+    tests/golden/pickkin_cases.npz as ``sort_quirk``), so the ``len`` and the ``dark`` column of a pick whose rate is
+    fitted each come out ascending on their own.  -> (counts per pick, rates of len, rates of dark)."""
+    counts = np.bincount(ids, minlength=n_picks)
+    offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    out = []
+    for name in ("len", "dark"):
+        values = events[name].to_numpy()
+        rates = backend.kinetic_rates(values, offsets)
+        if (rates.status == backend.CUMEXP_REFUSED).any():
+            raise ValueError(f"column {name!r}: the samples of a fit must be finite and must not be negative")
+        fitted = ~np.isnan(rates.a)
+        if fitted.any():
+            ascending = values[np.lexsort((values, ids))]
+            events[name] = np.where(fitted[ids], ascending, values)
+        out.append(rates)
+    return counts, out[0], out[1]
+
+
+def _progress(callback, n: int) -> None:
+    """The reference's calls: ``i`` before every pick, then the count.  ``"console"`` is accepted and shows nothing."""
+    if callable(callback):
+        for i in range(n):
+            callback(i)
+        callback(n)
+
+
+def evaluate_picks(picked_locs: list[pd.DataFrame], info: list[dict], *, max_dark_time: int = 3,
+                   progress_callback: Callable[[int], None] | Literal["console"] | None = None):
+    """Pick statistics (postprocess.py:1634-1746) -> (N, n_events, rmsd, rmsd_z, length, dark, new_locs), all picks in
+    one device pass: one link, one dark-time search, two ``backend.kinetic_rates`` calls, and the pandas float32 means of
+    the RMSD by the group statistics kernel (csrc/segment_stats.h's sums), in the reference's bits.  The reference leaves
+    the entries of empty picks uninitialised (``np.empty``); here they are NaN, as is all of ``rmsd_z`` without a ``z``
+    column.  A fit that ends on its iteration cap raises RuntimeError, where scipy's would.  ``progress_callback`` is
+    called as the reference calls it; ``"console"`` is accepted and ignored."""
+    pixelsize = lib.get_from_metadata(info, "Pixelsize", default=1.0)
+    n_picks = len(picked_locs)
+    N, n_events, rmsd, rmsd_z, length, dark = (np.full(n_picks, np.nan) for _ in range(6))
+    sizes = np.array([len(locs) for locs in picked_locs], np.int64)
+    filled = np.flatnonzero(sizes)
+    has_z = "z" in picked_locs[0].columns
+    _progress(progress_callback, n_picks)
+    N[filled] = sizes[filled]
+    if len(filled):
+        ids = np.repeat(filled, sizes[filled])
+        groups = backend.CenterGroups(ids)
+
+        def spread(names):
+            cols = [np.concatenate([picked_locs[k][c].to_numpy() for k in filled]) for c in names]
+            means = backend.group_mean_std(groups, cols)
+            rows = np.repeat(np.arange(len(filled)), sizes[filled])
+            with np.errstate(all="ignore"):
+                total = sum((col - mean.astype(col.dtype)[rows]) ** 2 for col, (mean, _) in zip(cols, means))
+                (mean_sq, _), = backend.group_mean_std(groups, [total])
+                return np.sqrt(mean_sq.astype(total.dtype))
+
+        rmsd[filled] = spread(("x", "y")) * pixelsize
+        if has_z:
+            rmsd_z[filled] = spread(("z",))
+    events, ids, linked_sizes = _pick_events(picked_locs, info, max_dark_time)
+    if (linked_sizes[filled] == 0).any():
+        raise ValueError("zero-size array to reduction operation maximum which has no identity")   # frame.max() of no event
+    if events is None:
+        raise ValueError("No objects to concatenate")
+    counts, len_rates, dark_rates = _pick_rates(events, ids, n_picks)
+    if ((len_rates.status | dark_rates.status)[filled] == backend.CUMEXP_ITER_CAP).any():
+        raise RuntimeError("Optimal parameters not found: a fit reached its iteration cap")
+    n_events[filled], length[filled], dark[filled] = counts[filled], len_rates.t[filled], dark_rates.t[filled]
+    return N, n_events, rmsd, rmsd_z, length, dark, events
+
+
+def _kept_picks(picked_locs: list[pd.DataFrame], info, max_dark_time):
+    """-> (the picks ``pick_kinetics`` keeps, their lengths, darks, event counts, their events), or None for none."""
+    n_picks = len(picked_locs)
+    events, ids, _ = _pick_events(picked_locs, info, max_dark_time)
+    if events is None or len(events) == 0:
+        return None
+    counts, len_rates, dark_rates = _pick_rates(events, ids, n_picks)
+    # the reference drops a pick whose curve_fit raises RuntimeError: here, one whose fit did not converge
+    kept = (counts > 0) & (len_rates.status == backend.CUMEXP_CONVERGED) & (dark_rates.status == backend.CUMEXP_CONVERGED)
+    if not kept.any():
+        return None
+    out_locs = events[kept[ids]].reset_index(drop=True)
+    return np.flatnonzero(kept), len_rates.t[kept], dark_rates.t[kept], counts[kept], out_locs
+
+
+def _pick_kinetics_single(pick_locs: pd.DataFrame, info: list[dict], max_dark_time: int):
+    """Kinetics of one picked region (postprocess.py:1749-1775) -> (events, length, dark), or None when the region has no
+    usable data or a fit does not converge."""
+    if not len(pick_locs):
+        return None
+    kept = _kept_picks([pick_locs], info, max_dark_time)
+    if kept is None:
+        return None
+    return kept[4], kept[1][0], kept[2][0]
+
+
+def pick_kinetics(picked_locs: list[pd.DataFrame], info: list[dict], *, max_dark_time: int = 3,
+                  progress_callback: Callable[[int], None] | Literal["console"] | None = None):
+    """Kinetics per picked region (postprocess.py:1778-1852) -> (length, dark, no_locs, out_locs), all picks in one
+    device pass (``_link_picks``, one dark-time search, two ``backend.kinetic_rates`` calls).  Picks without a binding
+    event that has a dark time are dropped, as in the reference, and so is a pick whose fit does not converge (the
+    reference drops it on scipy's RuntimeError).  ``out_locs`` has the reference's rows, columns and order, its in-place
+    sort of fitted ``len`` / ``dark`` columns included (``_pick_rates``).  Unlike the reference this does not write a
+    ``dark`` column into picks that came with ``len``.  ``progress_callback`` is called as the reference calls it;
+    ``"console"`` is accepted and ignored."""
+    _progress(progress_callback, len(picked_locs))
+    kept = _kept_picks(picked_locs, info, max_dark_time)
+    if kept is None:
+        raise ValueError("No objects to concatenate")
+    _, length, dark, no_locs, out_locs = kept
+    return length, dark, no_locs, out_locs
+
+
+def pick_properties(picked_locs: list[pd.DataFrame], info: list[dict], *, max_dark_time: int = 3,
+                    influx_rate: float = 0.03, pick_areas=None,
+                    kinetics_progress: Callable[[int], None] | Literal["console"] | None = None,
+                    groupprops_progress: Callable[[int], None] | Literal["console"] | None = None) -> pd.DataFrame:
+    """Pick properties (postprocess.py:1855-1917): ``pick_kinetics``, then ``groupprops`` of its events, then
+    ``n_units = 1 / (influx_rate * dark)``, ``locs``, ``length_cdf``, ``dark_cdf``, ``qpaint_idx_cdf = dark ** -1`` and the
+    optional ``pick_area_um2``."""
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", category=RuntimeWarning)
+        length, dark, no_locs, out_locs = pick_kinetics(picked_locs=picked_locs, info=info, max_dark_time=max_dark_time,
+                                                        progress_callback=kinetics_progress)
+        pick_props = groupprops(out_locs, callback=groupprops_progress)
+        if pick_areas is not None:
+            pick_props["pick_area_um2"] = pick_areas
+    with np.errstate(all="ignore"):
+        pick_props["n_units"] = 1 / (influx_rate * dark)
+        pick_props["locs"] = no_locs
+        pick_props["length_cdf"] = length
+        pick_props["dark_cdf"] = dark
+        pick_props["qpaint_idx_cdf"] = dark**-1
+    return pick_props
