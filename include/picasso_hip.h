@@ -38,6 +38,8 @@
  *                      fitting_method="gausslq"
  *   pmi_render_*       picasso/render.py:37-175 render -> :798-853 _render_hist,
  *                      :1020-1070 _render_gaussian (ang=None), :177-232, :451-467, :494-575
+ *   pmi_rotate_locs, pmi_render_*_rot  picasso/render.py:1571-1637 locs_rotation and the same renders with ang
+ *                      (:578-679 _draw_gaussian_rot_loc)
  *   pmi_blur*, pmi_render_blurred  picasso/render.py:1413-1460 _fftconvolve under :1349-1410
  *                      _render_smooth and :1249-1319 _render_convolve
  *   pmi_xcorr, pmi_rcc_pairs   picasso/imageprocess.py:27-50 xcorr, :53-161
@@ -410,6 +412,46 @@ int pmi_render_gaussian_dev(const float *d_x, const float *d_y, const float *d_l
                             int64_t N, double oversampling, double y_min, double x_min, double y_max,
                             double x_max, double min_blur_width, int iso, float *d_image, int64_t ny,
                             int64_t nx, int64_t *d_n_rendered, void *stream);
+
+/* ---- rotated views (picasso/render.py:1571-1637 locs_rotation; _render_hist / _render_gaussian / _render_gaussian_iso
+ * with ang; :578-679 _draw_gaussian_rot_loc) --- *
+ * x, y, z are the three coordinate columns of the table: all float32 (coords_f64 == 0, the usual table; the viewport's
+ * centre is then subtracted in float32, as on the float32 array the reference takes) or all float64 (coords_f64 != 0,
+ * what a table of mixed column types becomes).  matrix is the rotation as scipy gives it (float64[9], row major, a HOST
+ * pointer in both forms); matrix_f32 the same rounded to float32 (the covariance of the Gaussian).  The rows are rotated
+ * about the centre of the viewport, r_i = (M[i][0] v0 + M[i][1] v1) + M[i][2] v2 in float64 (N == 1:
+ * (M[i][0] v0 + M[i][2] v2) + M[i][1] v1, as scipy on a one-row array), and are in view when strictly inside it after
+ * the rotation.
+ *   pmi_rotate_locs       per row x' = os (x - x_min), y' = os (y - y_min), z' = os z and in_view (0 / 1): what
+ *                         locs_rotation returns before it drops the rows out of view
+ *   pmi_render_hist_rot   image[int(y'), int(x')] += 1 for the rows in view
+ *   pmi_render_gaussian_rot  the projection of the rotated 3-D Gaussian with widths os * max(lp, min_blur_width)
+ *                         (lpz NULL: twice the mean of lpx and lpy; iso != 0: sx = sy = their mean), float32 2x2 projected
+ *                         covariance, rows with det < 1e-10 counted and not drawn, +-3 sigma footprint, per pixel in
+ *                         TABLE ORDER  pix = float32(pix + norm * exp(-0.5 * e))  with glibc's exp.
+ * *n_rendered receives the number of rows in view.  The image is overwritten.  The Gaussian _dev form synchronises the
+ * stream once, as pmi_render_gaussian_dev.                                                                        */
+int pmi_rotate_locs(const void *x, const void *y, const void *z, int coords_f64, int64_t N, const double *matrix,
+                    double oversampling, double y_min, double x_min, double y_max, double x_max,
+                    double *xr, double *yr, double *zr, uint8_t *in_view);
+int pmi_rotate_locs_dev(const void *d_x, const void *d_y, const void *d_z, int coords_f64, int64_t N, const double *matrix,
+                        double oversampling, double y_min, double x_min, double y_max, double x_max,
+                        double *d_xr, double *d_yr, double *d_zr, uint8_t *d_in_view, void *stream);
+int pmi_render_hist_rot(const void *x, const void *y, const void *z, int coords_f64, int64_t N, const double *matrix,
+                        double oversampling, double y_min, double x_min, double y_max, double x_max,
+                        float *image, int64_t ny, int64_t nx, int64_t *n_rendered);
+int pmi_render_hist_rot_dev(const void *d_x, const void *d_y, const void *d_z, int coords_f64, int64_t N,
+                            const double *matrix, double oversampling, double y_min, double x_min, double y_max,
+                            double x_max, float *d_image, int64_t ny, int64_t nx, int64_t *d_n_rendered, void *stream);
+int pmi_render_gaussian_rot(const void *x, const void *y, const void *z, int coords_f64, const float *lpx,
+                            const float *lpy, const float *lpz, int64_t N, const double *matrix, const float *matrix_f32,
+                            double oversampling, double y_min, double x_min, double y_max, double x_max,
+                            double min_blur_width, int iso, float *image, int64_t ny, int64_t nx, int64_t *n_rendered);
+int pmi_render_gaussian_rot_dev(const void *d_x, const void *d_y, const void *d_z, int coords_f64, const float *d_lpx,
+                                const float *d_lpy, const float *d_lpz, int64_t N, const double *matrix,
+                                const float *matrix_f32, double oversampling, double y_min, double x_min, double y_max,
+                                double x_max, double min_blur_width, int iso, float *d_image, int64_t ny, int64_t nx,
+                                int64_t *d_n_rendered, void *stream);
 
 /* ---- image blur (picasso/render.py:1413-1460 _fftconvolve; the "smooth" and "convolve" renders) --- *
  * A separable blur of a float32 image of ny x nx pixels, axis 0 (y, weights wy, radius ry) first, then axis 1

@@ -92,6 +92,14 @@ SYMBOLS = {
     "pmi_render_hist_dev": (_i32, [_p, _p, _i64, _f64, _f64, _f64, _f64, _f64, _p, _i64, _i64, _p, _p]),
     "pmi_render_gaussian": (_i32, [_p, _p, _p, _p, _i64, _f64, _f64, _f64, _f64, _f64, _f64, _i32, _p, _i64, _i64, _p]),
     "pmi_render_gaussian_dev": (_i32, [_p, _p, _p, _p, _i64, _f64, _f64, _f64, _f64, _f64, _f64, _i32, _p, _i64, _i64, _p, _p]),
+    "pmi_rotate_locs": (_i32, [_p, _p, _p, _i32, _i64, _p, _f64, _f64, _f64, _f64, _f64, _p, _p, _p, _p]),
+    "pmi_rotate_locs_dev": (_i32, [_p, _p, _p, _i32, _i64, _p, _f64, _f64, _f64, _f64, _f64, _p, _p, _p, _p, _p]),
+    "pmi_render_hist_rot": (_i32, [_p, _p, _p, _i32, _i64, _p, _f64, _f64, _f64, _f64, _f64, _p, _i64, _i64, _p]),
+    "pmi_render_hist_rot_dev": (_i32, [_p, _p, _p, _i32, _i64, _p, _f64, _f64, _f64, _f64, _f64, _p, _i64, _i64, _p, _p]),
+    "pmi_render_gaussian_rot": (_i32, [_p, _p, _p, _i32, _p, _p, _p, _i64, _p, _p, _f64, _f64, _f64, _f64, _f64, _f64, _i32,
+                                       _p, _i64, _i64, _p]),
+    "pmi_render_gaussian_rot_dev": (_i32, [_p, _p, _p, _i32, _p, _p, _p, _i64, _p, _p, _f64, _f64, _f64, _f64, _f64, _f64,
+                                           _i32, _p, _i64, _i64, _p, _p]),
     "pmi_blur_dev": (_i32, [_p, _p, _i64, _i64, _p, _i64, _p, _i64, _i32, _f64, _p]),
     "pmi_blur": (_i32, [_p, _p, _i64, _i64, _p, _i64, _p, _i64, _i32, _f64]),
     "pmi_render_blurred": (_i32, [_p, _p, _i64, _f64, _f64, _f64, _f64, _f64, _p, _i64, _p, _i64, _i32, _f64, _p, _i64, _i64, _p]),

@@ -2159,6 +2159,79 @@ def render_blurred_arrays(x, y, oversampling, y_min, x_min, y_max, x_max, blur_w
     return int(n.value), image
 
 
+# ---- rotated views (csrc/render_rot.hip, picasso/render.py:1571-1637 locs_rotation and the renders with ang) -----------------
+def rotation_coords(x, y, z):
+    """The three coordinate columns as the rotated kernels take them -> (x, y, z, LINK type code): three float32 columns
+    stay float32, any other mix becomes float64, which is what ``locs[["x", "y", "z"]].to_numpy()`` makes of it."""
+    cols = [np.asarray(c) for c in (x, y, z)]
+    _check_rows(len(cols[0]), _PER_ROW, *cols)
+    dt = np.dtype(np.float32) if all(c.dtype == np.float32 for c in cols) else np.dtype(np.float64)
+    return tuple(np.ascontiguousarray(c, dt) for c in cols) + (link_type(dt, True),)
+
+
+def _rotation_matrices(matrix):
+    m = np.ascontiguousarray(matrix, np.float64)
+    if m.shape != (3, 3):
+        raise ValueError(f"a rotation matrix has shape (3, 3), not {m.shape}")
+    return m, np.ascontiguousarray(m, dtype=np.float32)
+
+
+def _rotate_locs_device(d_x, d_y, d_z, code, m64, view):
+    """pmi_rotate_locs_dev on resident columns -> (x', y', z' float64, in_view uint8) device tensors."""
+    import torch
+    n, dev = len(d_x), d_x.device
+    out = [_out(dev, torch.float64, n) for _ in range(3)] + [_out(dev, torch.uint8, n)]
+    _lib.call("pmi_rotate_locs_dev", _dptr(d_x), _dptr(d_y), _dptr(d_z), code, n, _lib.ptr(m64), *view,
+              *[_dptr(t) for t in out], _stream(dev))
+    return out
+
+
+def rotate_locs_arrays(x, y, z, matrix, oversampling, y_min, x_min, y_max, x_max):
+    """Every row rotated about the centre of the viewport -> (x', y', z' float64 in image units, in_view bool): what
+    ``locs_rotation`` returns before it drops the rows out of view."""
+    _lib.require_gpu()
+    x, y, z, code = rotation_coords(x, y, z)
+    m64, _ = _rotation_matrices(matrix)
+    view = (float(oversampling), float(y_min), float(x_min), float(y_max), float(x_max))
+    with _lib.lock():
+        d_x, d_y, d_z = (_to_device(c) for c in (x, y, z))
+        xr, yr, zr, in_view = (t.cpu().numpy() for t in _rotate_locs_device(d_x, d_y, d_z, code, m64, view))
+    return xr, yr, zr, in_view.astype(bool)
+
+
+def render_rot_arrays(x, y, z, matrix, oversampling, y_min, x_min, y_max, x_max, lpx=None, lpy=None, lpz=None,
+                      min_blur_width=0.0, iso=False, with_in_view=True):
+    """-> (n, image float32, in_view bool or None): the rotated view.  lpx / lpy None = histogram, else the projected
+    Gaussian (lpz None: twice the mean of lpx and lpy).  ``matrix`` is scipy's (3, 3) float64 rotation matrix; the
+    float32 copy the covariance takes is rounded here.  ``in_view`` marks the rows counted in n."""
+    import torch
+    _lib.require_gpu()
+    x, y, z, code = rotation_coords(x, y, z)
+    m64, m32 = _rotation_matrices(matrix)
+    n_y, n_x = render_dims(oversampling, y_min, x_min, y_max, x_max)
+    view = (float(oversampling), float(y_min), float(x_min), float(y_max), float(x_max))
+    widths = None
+    if lpx is not None:
+        widths = [np.ascontiguousarray(c, np.float32) for c in ((lpx, lpy) if lpz is None else (lpx, lpy, lpz))]
+        _check_rows(len(x), _PER_ROW, *widths)
+    with _lib.lock():
+        d_x, d_y, d_z = (_to_device(c) for c in (x, y, z))
+        dev = d_x.device
+        image, count = _out(dev, torch.float32, n_y, n_x), _out(dev, torch.int64, 1, zero=True)
+        if widths is None:
+            _lib.call("pmi_render_hist_rot_dev", _dptr(d_x), _dptr(d_y), _dptr(d_z), code, len(x), _lib.ptr(m64), *view,
+                      _dptr(image), n_y, n_x, _dptr(count), _stream(dev))
+        else:
+            d_w = [_to_device(c) for c in widths] + [None]
+            _lib.call("pmi_render_gaussian_rot_dev", _dptr(d_x), _dptr(d_y), _dptr(d_z), code, _dptr(d_w[0]), _dptr(d_w[1]),
+                      _dptr(d_w[2]), len(x), _lib.ptr(m64), _lib.ptr(m32), *view, float(min_blur_width), int(bool(iso)),
+                      _dptr(image), n_y, n_x, _dptr(count), _stream(dev))
+        in_view = _rotate_locs_device(d_x, d_y, d_z, code, m64, view)[3].cpu().numpy().astype(bool) if with_in_view else None
+        n = int(count.cpu()[0])
+        image = image.cpu().numpy()
+    return n, image, in_view
+
+
 # ---- kinetic rates of picks (csrc/cumexp.hip, picasso/lib.py:1263-1327) -----------------------------------------------------
 CUMEXP_CONVERGED, CUMEXP_ITER_CAP, CUMEXP_REFUSED = 0, 1, 2      # the status codes of pmi_cumexp_fit
 

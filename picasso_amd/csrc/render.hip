@@ -12,7 +12,8 @@
 //      columns), blur widths (float32), the clipped +-3 sigma footprint, the number of 32x32
 //      image tiles it touches;
 //   2. exclusive scan of those counts, emit (tile, localization) pairs in localization order,
-//      stable radix sort by tile  ->  every tile gets its localizations in table order;
+//      stable radix sort by tile  ->  every tile gets its localizations in table order
+//      (render_common.h, shared with the rotated view of render_rot.hip);
 //   3. one workgroup per tile: 256 threads x 4 pixels in registers; the tile's list is walked
 //      in chunks of 32 localizations whose 1-D profiles (float64 exp, rounded to float32 like
 //      the reference's gx / gy arrays) are built cooperatively in LDS, then every pixel adds
@@ -21,45 +22,18 @@
 //      with an inf or NaN profile value (inf * 0 = NaN) is added inside its footprint only.
 // The result is the reference's image bit for bit, up to a 1-ulp difference between the
 // device's and glibc's float64 exp surviving the rounding to float32.
-#include <algorithm>
-#include <cmath>
-#include <cstring>
-
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-
-#include "pmi_common.h"
+#include "render_common.h"
 
 #pragma clang fp contract(off)
 
 namespace pmi {
 namespace rend {
 
-constexpr int TILE = 32;
-constexpr int CHUNK = 32;          // localizations per LDS batch in the tile kernel
-
-struct View {
-    double oversampling, y_min, x_min, y_max, x_max;
-    float os_f, min_blur_f;
-    int iso;                 // gaussian_iso: both widths = their mean (render.py:1148-1216)
-    int64_t ny, nx;
-    int tiles_x, tiles_y;
-};
-
 struct Loc {              // one localization in view, image coordinates
     double x, y;
     float sx, sy;
     int i_min, i_max, j_min, j_max;      // clipped footprint [min, max); empty when max <= min
 };
-
-__device__ __forceinline__ float np_maxf(float a, float b) { return (a != a) ? a : ((b != b) ? b : (a > b ? a : b)); }
-
-// float64 -> int32 as the reference's compiled code does it on x86-64 (cvttsd2si): truncation, and
-// INT_MIN for NaN or out-of-range values — a NaN precision then yields an empty footprint.
-__device__ __forceinline__ int32_t to_int32(double v)
-{
-    return (v != v || v >= 2147483648.0 || v < -2147483648.0) ? (int32_t)0x80000000 : (int32_t)v;
-}
 
 __device__ __forceinline__ bool in_view(const View &v, float xf, float yf)
 {
@@ -117,32 +91,6 @@ __global__ void prep_kernel(const float *__restrict__ x, const float *__restrict
     }
     const unsigned long long bal = __ballot(ok);
     if ((threadIdx.x & 63) == 0 && bal) atomicAdd(n_rendered, (unsigned long long)__popcll(bal));
-}
-
-__global__ void emit_kernel(const Loc *__restrict__ locs, const unsigned *__restrict__ ntiles,
-                            const unsigned *__restrict__ offset, int64_t N, int tiles_x,
-                            unsigned *__restrict__ keys, unsigned *__restrict__ vals)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= N || ntiles[i] == 0) return;
-    const Loc L = locs[i];
-    unsigned o = offset[i];
-    for (int ty = L.i_min / TILE; ty <= (L.i_max - 1) / TILE; ty++)
-        for (int tx = L.j_min / TILE; tx <= (L.j_max - 1) / TILE; tx++) {
-            keys[o] = (unsigned)(ty * tiles_x + tx);
-            vals[o] = (unsigned)i;
-            o++;
-        }
-}
-
-__global__ void tile_bounds_kernel(const unsigned *__restrict__ keys, unsigned E, unsigned *__restrict__ start,
-                                   unsigned *__restrict__ end)
-{
-    const unsigned e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= E) return;
-    const unsigned k = keys[e];
-    if (e == 0 || keys[e - 1] != k) start[k] = e;
-    if (e + 1 == E || keys[e + 1] != k) end[k] = e + 1;
 }
 
 __global__ __launch_bounds__(256) void tile_kernel(const Loc *__restrict__ locs, const unsigned *__restrict__ vals,
@@ -229,21 +177,6 @@ __global__ __launch_bounds__(256) void tile_kernel(const Loc *__restrict__ locs,
     }
 }
 
-static int make_view(double oversampling, double y_min, double x_min, double y_max, double x_max, double min_blur,
-                     int64_t ny, int64_t nx, View *v)
-{
-    const int64_t ey = (int64_t)std::ceil(oversampling * (y_max - y_min));
-    const int64_t ex = (int64_t)std::ceil(oversampling * (x_max - x_min));
-    if (ny != ey || nx != ex) { set_error("render: image is %lld x %lld but the viewport needs %lld x %lld", (long long)ny, (long long)nx, (long long)ey, (long long)ex); return PMI_ERR_ARG; }
-    if (ny <= 0 || nx <= 0 || ny > 0x7fffffff || nx > 0x7fffffff) { set_error("render: bad image size"); return PMI_ERR_ARG; }
-    v->oversampling = oversampling; v->y_min = y_min; v->x_min = x_min; v->y_max = y_max; v->x_max = x_max;
-    v->os_f = (float)oversampling; v->min_blur_f = (float)min_blur; v->iso = 0;
-    v->ny = ny; v->nx = nx;
-    v->tiles_x = (int)((nx + TILE - 1) / TILE); v->tiles_y = (int)((ny + TILE - 1) / TILE);
-    if ((int64_t)v->tiles_x * v->tiles_y > 0x7fffffffLL) { set_error("render: image too large"); return PMI_ERR_ARG; }
-    return PMI_OK;
-}
-
 }  // namespace rend
 }  // namespace pmi
 
@@ -305,35 +238,10 @@ int pmi_render_gaussian_dev(const float *d_x, const float *d_y, const float *d_l
                        (unsigned long long *)d_n_rendered);
     PMI_HIP(hipGetLastError());
 
-    // exclusive scan -> offsets; the total decides the size of the pair buffers (one small D2H)
-    size_t tmp_bytes = 0;
-    PMI_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, ntiles, offset, 0u, (size_t)N, rocprim::plus<unsigned>(), s));
-    void *p_tmp = nullptr;
-    if ((rc = scratch(SCR_STAGE_D, tmp_bytes + 64, &p_tmp)) != PMI_OK) return rc;
-    PMI_HIP(rocprim::exclusive_scan(p_tmp, tmp_bytes, ntiles, offset, 0u, (size_t)N, rocprim::plus<unsigned>(), s));
-    unsigned last_off = 0, last_cnt = 0;
-    PMI_HIP(hipMemcpyAsync(&last_off, offset + (N - 1), 4, hipMemcpyDeviceToHost, s));
-    PMI_HIP(hipMemcpyAsync(&last_cnt, ntiles + (N - 1), 4, hipMemcpyDeviceToHost, s));
-    PMI_HIP(hipStreamSynchronize(s));
-    const uint64_t E = (uint64_t)last_off + last_cnt;
-    if (E > 0x7fffffffULL) { set_error("render: footprints cover %llu tiles in total, more than this kernel handles", (unsigned long long)E); return PMI_ERR_ARG; }
-
-    PMI_HIP(hipMemsetAsync(start, 0, (size_t)ntile * 8, s));
+    uint64_t E = 0;
+    unsigned *vals2 = nullptr;
+    if ((rc = rend::tile_lists(locs, ntiles, offset, N, v, start, &E, &vals2, s)) != PMI_OK) return rc;
     if (E > 0) {
-        void *p_pairs = nullptr;
-        if ((rc = scratch(SCR_RECORDS, (size_t)E * 16 + 64, &p_pairs)) != PMI_OK) return rc;
-        unsigned *keys = (unsigned *)p_pairs, *vals = keys + E, *keys2 = vals + E, *vals2 = keys2 + E;
-        hipLaunchKernelGGL(rend::emit_kernel, dim3(nb), dim3(256), 0, s, locs, ntiles, offset, N, v.tiles_x, keys, vals);
-        PMI_HIP(hipGetLastError());
-        int bits = 1;
-        while ((1LL << bits) < ntile) bits++;
-        size_t sort_bytes = 0;
-        PMI_HIP(rocprim::radix_sort_pairs(nullptr, sort_bytes, keys, keys2, vals, vals2, (size_t)E, 0, bits, s));
-        void *p_sort = nullptr;
-        if ((rc = scratch(SCR_RECORDS2, sort_bytes + 64, &p_sort)) != PMI_OK) return rc;
-        PMI_HIP(rocprim::radix_sort_pairs(p_sort, sort_bytes, keys, keys2, vals, vals2, (size_t)E, 0, bits, s));   // stable
-        hipLaunchKernelGGL(rend::tile_bounds_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, s, keys2, (unsigned)E, start, end);
-        PMI_HIP(hipGetLastError());
         hipLaunchKernelGGL(rend::tile_kernel, dim3((unsigned)ntile), dim3(256), 0, s, locs, vals2, start, end, v, d_image);
     } else {
         PMI_HIP(hipMemsetAsync(d_image, 0, (size_t)ny * nx * sizeof(float), s));

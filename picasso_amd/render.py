@@ -4,8 +4,18 @@ widths = localization precisions) and ``"gaussian_iso"`` (one width, their mean)
 :798-853 ``_render_hist``, :1020-1070 ``_render_gaussian``; the pixels are computed by
 csrc/render.hip.  The two blurred histograms, ``_render_smooth`` (:1349-1410) and ``_render_convolve`` (:1249-1319)
 with ``_fftconvolve`` (:1413-1460) under them, are computed by csrc/blur.hip and called by name: ``render()`` still
-refuses ``blur_method="smooth"`` / ``"convolve"``.  Rotated views (``ang``) are not built; they
-raise instead of falling back to a CPU path.
+refuses ``blur_method="smooth"`` / ``"convolve"``.
+
+Rotated views (``ang``: a scipy ``Rotation`` or the legacy Euler tuple).  ``_render_hist``,
+``_render_gaussian`` and ``_render_gaussian_iso`` (and their older public names) draw them on the device
+(csrc/render_rot.hip), in the reference's bits; ``rotation_matrix``, ``to_rotation``, ``closest_rotvec`` and
+``locs_rotation`` (picasso/render.py:1463-1637) are here as well, the last one rotating on the device.  The 3x3 matrix
+is always scipy's own (``to_rotation(ang).as_matrix()``): the Euler tuple goes through ``Rotation.from_matrix``, which
+re-orthogonalises, so the device never rebuilds it from angles.  The widths are taken as float32 columns, as in the flat
+view.  The one follow-up, pinned by tests that predate the kernels: ``render(..., ang=...)`` and ``_render_smooth`` /
+``_render_convolve`` (and their older names) with ``ang`` still raise ``NotImplementedError``, and
+``localize.install()`` still hands rotated ``_render_gaussian`` / ``_render_hist`` calls to the reference's functions.
+``backend.render_rot_arrays`` already returns the in-view mask a rotated ``_render_convolve`` needs for its medians.
 
 Zero blur width.  The reference draws each localization in ``_draw_gaussian_loc``, compiled by numba
 with Python's error model, so ``1.0 / (2.0 * sx_ * sx_)`` raises ``ZeroDivisionError`` when a
@@ -25,6 +35,7 @@ from __future__ import annotations
 
 import numpy as np
 import pandas as pd
+from scipy.spatial.transform import Rotation
 
 from . import backend, lib
 
@@ -51,7 +62,8 @@ def render(locs: pd.DataFrame, info, oversampling: float = 1.0, viewport=None, b
     oversampling = pixelsize / disp_px_size
     (y_min, x_min), (y_max, x_max) = _viewport(info, viewport)
     if ang is not None:
-        raise NotImplementedError("rotated rendering (ang) has no HIP kernel in picasso_amd")
+        raise NotImplementedError("rotated rendering (ang) is not routed through render() yet: call _render_hist, "
+                                  "_render_gaussian or _render_gaussian_iso with ang (csrc/render_rot.hip)")
     if blur_method is None:
         return _render_hist(locs, oversampling, y_min, x_min, y_max, x_max)
     if blur_method == "gaussian":
@@ -99,13 +111,13 @@ def _raise_on_zero_width(x, y, lpx, lpy, oversampling, y_min, x_min, y_max, x_ma
 
 def _render_hist(locs, oversampling, y_min, x_min, y_max, x_max, ang=None):
     if ang is not None:
-        raise NotImplementedError("rotated rendering (ang) has no HIP kernel in picasso_amd")
+        return _render_rotated(locs, oversampling, y_min, x_min, y_max, x_max, ang)
     return backend.render_arrays(locs["x"].to_numpy(), locs["y"].to_numpy(), oversampling, y_min, x_min, y_max, x_max)
 
 
 def _render_gaussian(locs, oversampling, y_min, x_min, y_max, x_max, min_blur_width, ang=None):
     if ang is not None:
-        raise NotImplementedError("rotated rendering (ang) has no HIP kernel in picasso_amd")
+        return _render_rotated(locs, oversampling, y_min, x_min, y_max, x_max, ang, min_blur_width, iso=False)
     x, y, lpx, lpy = (locs[c].to_numpy() for c in ("x", "y", "lpx", "lpy"))
     _raise_on_zero_width(x, y, lpx, lpy, oversampling, y_min, x_min, y_max, x_max, min_blur_width, False)
     return backend.render_arrays(x, y, oversampling, y_min, x_min, y_max, x_max, lpx=lpx, lpy=lpy,
@@ -115,7 +127,7 @@ def _render_gaussian(locs, oversampling, y_min, x_min, y_max, x_max, min_blur_wi
 def _render_gaussian_iso(locs, oversampling, y_min, x_min, y_max, x_max, min_blur_width, ang=None):
     """picasso/render.py:1148-1216: one isotropic width per localization, the mean of the two."""
     if ang is not None:
-        raise NotImplementedError("rotated rendering (ang) has no HIP kernel in picasso_amd")
+        return _render_rotated(locs, oversampling, y_min, x_min, y_max, x_max, ang, min_blur_width, iso=True)
     x, y, lpx, lpy = (locs[c].to_numpy() for c in ("x", "y", "lpx", "lpy"))
     _raise_on_zero_width(x, y, lpx, lpy, oversampling, y_min, x_min, y_max, x_max, min_blur_width, True)
     return backend.render_arrays(x, y, oversampling, y_min, x_min, y_max, x_max, lpx=lpx, lpy=lpy,
@@ -124,7 +136,64 @@ def _render_gaussian_iso(locs, oversampling, y_min, x_min, y_max, x_max, min_blu
 
 def _refuse_ang(ang) -> None:
     if ang is not None:
-        raise NotImplementedError("rotated rendering (ang) has no HIP kernel in picasso_amd")
+        raise NotImplementedError("rotated rendering (ang) of the blurred histograms is not routed to the device yet "
+                                  "(module docstring); _render_hist, _render_gaussian and _render_gaussian_iso take ang")
+
+
+# ---- rotated views (picasso/render.py:1463-1637) -------------------------------------------------------------------------
+def rotation_matrix(angx: float, angy: float, angz: float) -> Rotation:
+    """The legacy Euler convention: the product of the rotations about x, y and z (radians), in that order, handed to
+    ``Rotation.from_matrix`` (which re-orthogonalises it)."""
+    cx, sx, cy, sy, cz, sz = np.cos(angx), np.sin(angx), np.cos(angy), np.sin(angy), np.cos(angz), np.sin(angz)
+    about_x = np.array([[1.0, 0.0, 0.0], [0.0, cx, sx], [0.0, -sx, cx]])
+    about_y = np.array([[cy, 0.0, sy], [0.0, 1.0, 0.0], [-sy, 0.0, cy]])
+    about_z = np.array([[cz, -sz, 0.0], [sz, cz, 0.0], [0.0, 0.0, 1.0]])
+    return Rotation.from_matrix(about_x @ about_y @ about_z)
+
+
+def to_rotation(ang: tuple[float, float, float] | Rotation | None) -> Rotation | None:
+    """None stays None, a scipy ``Rotation`` is used as it is, a tuple of three angles goes through ``rotation_matrix``."""
+    if ang is None or isinstance(ang, Rotation):
+        return ang
+    return rotation_matrix(*ang)
+
+
+def closest_rotvec(rotation: Rotation, reference: lib.FloatArray1D) -> lib.FloatArray1D:
+    """The rotation vector of ``rotation`` with the number of full turns about its axis that brings it closest to the
+    rotation vector ``reference`` (its magnitude may exceed pi).  The identity keeps the reference's axis and whole turns."""
+    reference = np.asarray(reference, dtype=float)
+    full_turn = 2 * np.pi
+    rotvec = rotation.as_rotvec()
+    angle = np.linalg.norm(rotvec)
+    if angle < 1e-9:
+        length = np.linalg.norm(reference)
+        if length < 1e-9:
+            return np.zeros(3)
+        return reference * (full_turn * np.round(length / full_turn) / length)
+    axis = rotvec / angle
+    turns = np.round((axis @ reference - angle) / full_turn)
+    return axis * (angle + full_turn * turns)
+
+
+def locs_rotation(locs: pd.DataFrame, oversampling: float, x_min: float, x_max: float, y_min: float, y_max: float,
+                  ang: tuple[float, float, float] | Rotation) -> tuple[lib.FloatArray1D, lib.FloatArray1D, lib.BoolArray1D, lib.FloatArray1D]:
+    """-> (x, y, in_view, z): the rows rotated about the centre of the field of view (csrc/render_rot.hip), those left
+    strictly inside it, in display pixels; ``in_view`` marks them in the table.  Note the argument order."""
+    x, y, z, in_view = backend.rotate_locs_arrays(locs["x"].to_numpy(), locs["y"].to_numpy(), locs["z"].to_numpy(),
+                                                  to_rotation(ang).as_matrix(), oversampling, y_min, x_min, y_max, x_max)
+    return x[in_view], y[in_view], in_view, z[in_view]
+
+
+def _render_rotated(locs, oversampling, y_min, x_min, y_max, x_max, ang, min_blur_width=None, iso=False):
+    """The rotated histogram (``min_blur_width`` None) or projected Gaussian in one device call -> (n, image)."""
+    widths = {}
+    if min_blur_width is not None:
+        widths = dict(lpx=locs["lpx"].to_numpy(), lpy=locs["lpy"].to_numpy(),
+                      lpz=locs["lpz"].to_numpy() if "lpz" in locs else None, min_blur_width=min_blur_width, iso=iso)
+    n, image, _ = backend.render_rot_arrays(locs["x"].to_numpy(), locs["y"].to_numpy(), locs["z"].to_numpy(),
+                                            to_rotation(ang).as_matrix(), oversampling, y_min, x_min, y_max, x_max,
+                                            with_in_view=False, **widths)
+    return n, image
 
 
 def _fftconvolve(image: lib.FloatArray2D, blur_width: float, blur_height: float) -> lib.FloatArray2D:
