@@ -88,12 +88,18 @@ def golden_rounds(g, name):
     frame = fr + 1 - fr.min()
     bounds = np.concatenate((np.arange(0, n_frames, seg_len), [n_frames]))
     first = frame <= seg_len
-    cols = {"xy1": (XY_F32, g[p + "in_x"], g[p + "in_y"], None),
-            "xy2": (XY_F64, g[p + "round_xy2_x"], g[p + "round_xy2_y"], None)}
+    # the key mode follows the dtype of the columns, as in picasso_amd/aim.py (aim() itself: float32 in round 1, float64
+    # after); a fixture of single rounds (aim_edge_cases.npz) stores only the rounds it ran
+    single = lambda a: a.dtype == np.float32  # noqa: E731
+    cols = {"xy1": (XY_F32 if single(g[p + "in_x"]) and single(g[p + "in_y"]) else XY_F64, g[p + "in_x"], g[p + "in_y"], None)}
+    if p + "round_xy2_x" in g:
+        cols["xy2"] = (XY_F64, g[p + "round_xy2_x"], g[p + "round_xy2_y"], None)
     if p + "round_z1_z" in g:
         zx, zy = g[p + "round_z1_x"], g[p + "round_z1_y"]
-        cols["z1"] = (Z_F32, zx, zy, g[p + "round_z1_z"] / pixelsize)
-        cols["z2"] = (Z_F64, zx, zy, g[p + "round_z2_z"] / pixelsize)
+        z1 = g[p + "round_z1_z"] / pixelsize
+        cols["z1"] = (Z_F32 if single(z1) else Z_F64, zx, zy, z1)
+        if p + "round_z2_z" in g:
+            cols["z2"] = (Z_F64, zx, zy, g[p + "round_z2_z"] / pixelsize)
     rounds, segs = g[p + "rec_round"], g[p + "rec_seg"]
     lens, peaks = g[p + "rec_len"], g[p + "rec_peak"]
     starts = np.concatenate(([0], np.cumsum(lens)))
