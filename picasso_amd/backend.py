@@ -335,31 +335,41 @@ def zfit_arrays(sx, sy, cx, cy):
     return z, sq
 
 
+def _viewport(oversampling, y_min, x_min, y_max, x_max, image=True):
+    """-> (the five floats as the C calls take them, (n_y, n_x) of the image by pmi_render_dims, render.py:224-225);
+    a viewport without pixels raises ValueError.  ``image=False``: a call that draws nothing (``rotate_locs_arrays``)
+    takes the floats alone, whatever the viewport holds.  Needs no GPU."""
+    view = (float(oversampling), float(y_min), float(x_min), float(y_max), float(x_max))
+    if not image:
+        return view, None
+    ny, nx = ctypes.c_int64(), ctypes.c_int64()
+    _lib.call("pmi_render_dims", *view, ctypes.byref(ny), ctypes.byref(nx))
+    if ny.value <= 0 or nx.value <= 0:
+        raise ValueError("empty viewport")
+    return view, (int(ny.value), int(nx.value))
+
+
+def render_dims(oversampling, y_min, x_min, y_max, x_max):
+    """(n_y, n_x) of a render (render.py:224-225); needs no GPU."""
+    return _viewport(oversampling, y_min, x_min, y_max, x_max)[1]
+
+
 def render_arrays(x, y, oversampling, y_min, x_min, y_max, x_max, lpx=None, lpy=None, min_blur_width=0.0, iso=False):
     """-> (n, image float32).  lpx/lpy None = histogram, else the Gaussian render."""
     _lib.require_gpu()
-    L = _lib.load()
     x = np.ascontiguousarray(x, np.float32)
     y = np.ascontiguousarray(y, np.float32)
-    N = len(x)
-    ny, nx = ctypes.c_int64(), ctypes.c_int64()
-    _lib.check(L.pmi_render_dims(float(oversampling), float(y_min), float(x_min), float(y_max), float(x_max),
-                                 ctypes.byref(ny), ctypes.byref(nx)), "pmi_render_dims")
-    if ny.value <= 0 or nx.value <= 0:
-        raise ValueError("empty viewport")
-    image = np.empty((ny.value, nx.value), np.float32)
+    view, (n_y, n_x) = _viewport(oversampling, y_min, x_min, y_max, x_max)
+    image = np.empty((n_y, n_x), np.float32)
     n = ctypes.c_int64(0)
     with _lib.lock():
         if lpx is None:
-            rc = L.pmi_render_hist(_lib.ptr(x), _lib.ptr(y), N, float(oversampling), float(y_min), float(x_min),
-                                   float(y_max), float(x_max), _lib.ptr(image), ny.value, nx.value, ctypes.byref(n))
+            _lib.call("pmi_render_hist", _lib.ptr(x), _lib.ptr(y), len(x), *view, _lib.ptr(image), n_y, n_x, ctypes.byref(n))
         else:
             lpx = np.ascontiguousarray(lpx, np.float32)
             lpy = np.ascontiguousarray(lpy, np.float32)
-            rc = L.pmi_render_gaussian(_lib.ptr(x), _lib.ptr(y), _lib.ptr(lpx), _lib.ptr(lpy), N, float(oversampling),
-                                       float(y_min), float(x_min), float(y_max), float(x_max), float(min_blur_width),
-                                       int(bool(iso)), _lib.ptr(image), ny.value, nx.value, ctypes.byref(n))
-    _lib.check(rc, "pmi_render")
+            _lib.call("pmi_render_gaussian", _lib.ptr(x), _lib.ptr(y), _lib.ptr(lpx), _lib.ptr(lpy), len(x), *view,
+                      float(min_blur_width), int(bool(iso)), _lib.ptr(image), n_y, n_x, ctypes.byref(n))
     return int(n.value), image
 
 
@@ -1964,19 +1974,14 @@ def render_hist_device(x, y, oversampling, y_min, x_min, y_max, x_max):
     """The histogram render (``render_arrays`` without widths) that stays on the device -> (n, float32 device tensor)."""
     import torch
     _lib.require_gpu()
-    ny, nx = ctypes.c_int64(), ctypes.c_int64()
-    _lib.call("pmi_render_dims", float(oversampling), float(y_min), float(x_min), float(y_max), float(x_max),
-              ctypes.byref(ny), ctypes.byref(nx))
-    if ny.value <= 0 or nx.value <= 0:
-        raise ValueError("empty viewport")
-    if max(ny.value, nx.value) > FRC_MAX_SIDE + 1:
-        raise MemoryError(f"a render of {ny.value} x {nx.value} pixels exceeds the FRC limit of {FRC_MAX_SIDE} per side")
+    view, (n_y, n_x) = _viewport(oversampling, y_min, x_min, y_max, x_max)
+    if max(n_y, n_x) > FRC_MAX_SIDE + 1:
+        raise MemoryError(f"a render of {n_y} x {n_x} pixels exceeds the FRC limit of {FRC_MAX_SIDE} per side")
     d_x, d_y = _to_device(x, np.float32), _to_device(y, np.float32)
-    image = torch.empty((ny.value, nx.value), dtype=torch.float32, device=d_x.device)
+    image = torch.empty((n_y, n_x), dtype=torch.float32, device=d_x.device)
     count = torch.zeros(1, dtype=torch.int64, device=d_x.device)
     with _lib.lock():
-        _lib.call("pmi_render_hist_dev", _dptr(d_x), _dptr(d_y), len(d_x), float(oversampling), float(y_min), float(x_min),
-                  float(y_max), float(x_max), _dptr(image), ny.value, nx.value, _dptr(count), None)
+        _lib.call("pmi_render_hist_dev", _dptr(d_x), _dptr(d_y), len(d_x), *view, _dptr(image), n_y, n_x, _dptr(count), None)
         n = int(count.cpu()[0])
     return n, image
 
@@ -2132,20 +2137,10 @@ def blur_array(image, blur_width, blur_height) -> np.ndarray:
     return blur_with_plan(image, blur_plan(shape[0], shape[1], blur_width, blur_height))
 
 
-def render_dims(oversampling, y_min, x_min, y_max, x_max):
-    """(n_y, n_x) of a render (render.py:224-225); needs no GPU."""
-    ny, nx = ctypes.c_int64(), ctypes.c_int64()
-    _lib.call("pmi_render_dims", float(oversampling), float(y_min), float(x_min), float(y_max), float(x_max),
-              ctypes.byref(ny), ctypes.byref(nx))
-    if ny.value <= 0 or nx.value <= 0:
-        raise ValueError("empty viewport")
-    return int(ny.value), int(nx.value)
-
-
 def render_blurred_arrays(x, y, oversampling, y_min, x_min, y_max, x_max, blur_width, blur_height):
     """-> (n, image float32): the histogram render followed by ``_fftconvolve(image, blur_width, blur_height)`` in one
     call; the histogram never leaves the device."""
-    n_y, n_x = render_dims(oversampling, y_min, x_min, y_max, x_max)
+    view, (n_y, n_x) = _viewport(oversampling, y_min, x_min, y_max, x_max)
     plan = blur_plan(n_y, n_x, blur_width, blur_height)
     _lib.require_gpu()
     x = np.ascontiguousarray(x, np.float32)
@@ -2154,8 +2149,7 @@ def render_blurred_arrays(x, y, oversampling, y_min, x_min, y_max, x_max, blur_w
     n = ctypes.c_int64(0)
     tail, keep = _blur_args(plan)
     with _lib.lock():
-        _lib.call("pmi_render_blurred", _lib.ptr(x), _lib.ptr(y), len(x), float(oversampling), float(y_min), float(x_min),
-                  float(y_max), float(x_max), *tail, _lib.ptr(image), n_y, n_x, ctypes.byref(n))
+        _lib.call("pmi_render_blurred", _lib.ptr(x), _lib.ptr(y), len(x), *view, *tail, _lib.ptr(image), n_y, n_x, ctypes.byref(n))
     return int(n.value), image
 
 
@@ -2192,7 +2186,7 @@ def rotate_locs_arrays(x, y, z, matrix, oversampling, y_min, x_min, y_max, x_max
     _lib.require_gpu()
     x, y, z, code = rotation_coords(x, y, z)
     m64, _ = _rotation_matrices(matrix)
-    view = (float(oversampling), float(y_min), float(x_min), float(y_max), float(x_max))
+    view, _ = _viewport(oversampling, y_min, x_min, y_max, x_max, image=False)
     with _lib.lock():
         d_x, d_y, d_z = (_to_device(c) for c in (x, y, z))
         xr, yr, zr, in_view = (t.cpu().numpy() for t in _rotate_locs_device(d_x, d_y, d_z, code, m64, view))
@@ -2208,8 +2202,7 @@ def render_rot_arrays(x, y, z, matrix, oversampling, y_min, x_min, y_max, x_max,
     _lib.require_gpu()
     x, y, z, code = rotation_coords(x, y, z)
     m64, m32 = _rotation_matrices(matrix)
-    n_y, n_x = render_dims(oversampling, y_min, x_min, y_max, x_max)
-    view = (float(oversampling), float(y_min), float(x_min), float(y_max), float(x_max))
+    view, (n_y, n_x) = _viewport(oversampling, y_min, x_min, y_max, x_max)
     widths = None
     if lpx is not None:
         widths = [np.ascontiguousarray(c, np.float32) for c in ((lpx, lpy) if lpz is None else (lpx, lpy, lpz))]

@@ -18,9 +18,10 @@
 // windows of samples the chunk reads (the far side l - j and the near side l + j of every output of its tile) and the
 // chunk's weights in LDS.  Every weight and every sample is staged once per workgroup and tile; the accumulators stay in
 // registers across chunks.  No atomics, no float32 accumulation, contraction off.
-#include <cmath>
-
-#include "pmi_common.h"
+//
+// The image limits (rend::check_image), the staging of the host forms (rend::Staged) and the table of scratch slots are
+// render_common.h's: pmi_blur_dev keeps the image between the passes in SCR_STAGE_D, the host forms everything in SCR_STAGE_A.
+#include "render_common.h"
 
 #include "blur_core.h"
 
@@ -135,14 +136,6 @@ __global__ void scale_copy_kernel(const float *__restrict__ in, float *__restric
 
 static unsigned grid_of(int64_t ntiles) { return (unsigned)(ntiles < (int64_t)MAX_GRID ? ntiles : (int64_t)MAX_GRID); }
 
-// the render's own limit (render.hip make_view): sides below 2^31 and at most 2^31 - 1 tiles of 32 x 32 pixels
-static int check_image(int64_t ny, int64_t nx)
-{
-    if (ny <= 0 || nx <= 0 || ny > 0x7fffffff || nx > 0x7fffffff) { set_error("blur: bad image size %lld x %lld", (long long)ny, (long long)nx); return PMI_ERR_ARG; }
-    if (((ny + 31) / 32) * ((nx + 31) / 32) > 0x7fffffffLL) { set_error("blur: image too large"); return PMI_ERR_ARG; }
-    return PMI_OK;
-}
-
 }  // namespace blur
 }  // namespace pmi
 
@@ -152,7 +145,7 @@ int pmi_blur_dev(const float *d_in, float *d_out, int64_t ny, int64_t nx, const 
                  const double *d_wx, int64_t rx, int round_between, double scale, void *stream)
 {
     using namespace pmi;
-    int rc = blur::check_image(ny, nx);
+    int rc = rend::check_image("blur", ny, nx);
     if (rc != PMI_OK) return rc;
     if (!d_in || !d_out || d_in == d_out) { set_error("blur: input and output must be two device images"); return PMI_ERR_ARG; }
     if ((d_wy && ry < 0) || (d_wx && rx < 0) || ry > 0x3fffffff || rx > 0x3fffffff) { set_error("blur: bad radius"); return PMI_ERR_ARG; }
@@ -162,8 +155,8 @@ int pmi_blur_dev(const float *d_in, float *d_out, int64_t ny, int64_t nx, const 
     const int64_t row_tx = (nx + blur::ROW_T - 1) / blur::ROW_T, row_n = row_tx * ny;
     constexpr int COL_LANES = blur::COL_X * blur::COL_Y / blur::COL_PER;
     if (d_wy && d_wx) {
-        void *mid = nullptr;
-        if ((rc = scratch(SCR_STAGE_D, (size_t)ny * nx * (round_between ? 4 : 8) + 64, &mid)) != PMI_OK) return rc;
+        char *mid = nullptr;               // the image between the passes, float32 or float64
+        if ((rc = rows::carve(SCR_STAGE_D, [&](rows::Arena &a) { mid = a.take<char>((size_t)ny * nx * (round_between ? 4 : 8)); })) != PMI_OK) return rc;
         if (round_between) {
             hipLaunchKernelGGL(blur::col_pass_kernel<float>, dim3(blur::grid_of(col_n)), dim3(COL_LANES), 0, s, d_in, (float *)mid, ny, nx,
                                d_wy, ry, 0, 1.0, col_tx, col_n);
@@ -193,18 +186,13 @@ int pmi_blur_dev(const float *d_in, float *d_out, int64_t ny, int64_t nx, const 
     return PMI_OK;
 }
 
-// weights of both axes behind each other in SCR_STAGE_C -> device pointers (nullptr for a skipped axis)
-static int stage_weights(const double *wy, int64_t ry, const double *wx, int64_t rx, const double **d_wy, const double **d_wx)
+// the weights of both axes named to `st`; a skipped axis has no piece and keeps its nullptr
+static int stage_weights(pmi::rend::Staged &st, const double *wy, int64_t ry, const double *wx, int64_t rx, double *&d_wy, double *&d_wx)
 {
     using namespace pmi;
     if ((wy && ry < 0) || (wx && rx < 0) || ry > 0x3fffffff || rx > 0x3fffffff) { set_error("blur: bad radius"); return PMI_ERR_ARG; }
-    const size_t n_y = wy ? (size_t)(2 * ry + 1) : 0, n_x = wx ? (size_t)(2 * rx + 1) : 0;
-    void *d_w = nullptr;
-    int rc = scratch(SCR_STAGE_C, (n_y + n_x) * 8 + 64, &d_w);
-    if (rc != PMI_OK) return rc;
-    *d_wy = *d_wx = nullptr;
-    if (wy) { PMI_HIP(hipMemcpy(d_w, wy, n_y * 8, hipMemcpyHostToDevice)); *d_wy = (const double *)d_w; }
-    if (wx) { PMI_HIP(hipMemcpy((double *)d_w + n_y, wx, n_x * 8, hipMemcpyHostToDevice)); *d_wx = (const double *)d_w + n_y; }
+    if (wy) st.add(d_wy, (size_t)(2 * ry + 1), wy);
+    if (wx) st.add(d_wx, (size_t)(2 * rx + 1), wx);
     return PMI_OK;
 }
 
@@ -214,18 +202,15 @@ int pmi_blur(const float *in, float *out, int64_t ny, int64_t nx, const double *
     using namespace pmi;
     if (pmi_device_count() < 1) { set_error("no HIP device"); return PMI_ERR_NODEVICE; }
     if (!in || !out) { set_error("null pointer"); return PMI_ERR_ARG; }
-    int rc = blur::check_image(ny, nx);
+    int rc = rend::check_image("blur", ny, nx);
     if (rc != PMI_OK) return rc;
-    const size_t bytes = (size_t)ny * nx * 4;
-    void *d_in = nullptr, *d_out = nullptr;
-    const double *d_wy = nullptr, *d_wx = nullptr;
-    if ((rc = scratch(SCR_STAGE_A, bytes + 64, &d_in)) != PMI_OK) return rc;
-    if ((rc = scratch(SCR_STAGE_B, bytes + 64, &d_out)) != PMI_OK) return rc;
-    if ((rc = stage_weights(wy, ry, wx, rx, &d_wy, &d_wx)) != PMI_OK) return rc;
-    PMI_HIP(hipMemcpy(d_in, in, bytes, hipMemcpyHostToDevice));
-    if ((rc = pmi_blur_dev((const float *)d_in, (float *)d_out, ny, nx, d_wy, ry, d_wx, rx, round_between, scale, nullptr)) != PMI_OK) return rc;
-    PMI_HIP(hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost));
-    return PMI_OK;
+    float *d_in = nullptr, *d_out = nullptr;
+    double *d_wy = nullptr, *d_wx = nullptr;
+    rend::Staged st;
+    st.add(d_in, (size_t)ny * nx, in), st.add(d_out, (size_t)ny * nx, nullptr, out);
+    if ((rc = stage_weights(st, wy, ry, wx, rx, d_wy, d_wx)) != PMI_OK || (rc = st.place()) != PMI_OK) return rc;
+    rc = pmi_blur_dev(d_in, d_out, ny, nx, d_wy, ry, d_wx, rx, round_between, scale, nullptr);
+    return rc != PMI_OK ? rc : st.fetch();
 }
 
 int pmi_render_blurred(const float *x, const float *y, int64_t N, double oversampling, double y_min, double x_min,
@@ -235,28 +220,20 @@ int pmi_render_blurred(const float *x, const float *y, int64_t N, double oversam
     using namespace pmi;
     if (pmi_device_count() < 1) { set_error("no HIP device"); return PMI_ERR_NODEVICE; }
     if (!image || !n_rendered || (N > 0 && (!x || !y))) { set_error("null pointer"); return PMI_ERR_ARG; }
-    int rc = blur::check_image(ny, nx);
+    int rc = rend::check_image("blur", ny, nx);
     if (rc != PMI_OK) return rc;
-    const size_t col = (size_t)(N > 0 ? N : 1) * 4;
-    const size_t bytes = (((size_t)ny * nx * 4 + 7) / 8) * 8;
-    void *d_xy = nullptr, *d_hist = nullptr, *d_out = nullptr;
-    const double *d_wy = nullptr, *d_wx = nullptr;
-    if ((rc = scratch(SCR_STAGE_A, col * 2 + 64, &d_xy)) != PMI_OK) return rc;
-    if ((rc = scratch(SCR_IDS, bytes + 8, &d_hist)) != PMI_OK) return rc;
-    if ((rc = scratch(SCR_STAGE_B, bytes + 64, &d_out)) != PMI_OK) return rc;
-    if ((rc = stage_weights(wy, ry, wx, rx, &d_wy, &d_wx)) != PMI_OK) return rc;
-    float *dx = (float *)d_xy, *dy = dx + N;
-    int64_t *dn = (int64_t *)((char *)d_hist + bytes);
-    if (N > 0) {
-        PMI_HIP(hipMemcpy(dx, x, (size_t)N * 4, hipMemcpyHostToDevice));
-        PMI_HIP(hipMemcpy(dy, y, (size_t)N * 4, hipMemcpyHostToDevice));
-    }
+    float *dx = nullptr, *dy = nullptr, *d_hist = nullptr, *d_out = nullptr;
+    double *d_wy = nullptr, *d_wx = nullptr;
+    int64_t *dn = nullptr;
+    const size_t n = (size_t)(N > 0 ? N : 0);
+    rend::Staged st;
+    st.add(dx, n, x), st.add(dy, n, y), st.add(d_hist, (size_t)ny * nx), st.add(dn, 1, nullptr, n_rendered);
+    st.add(d_out, (size_t)ny * nx, nullptr, image);
+    if ((rc = stage_weights(st, wy, ry, wx, rx, d_wy, d_wx)) != PMI_OK || (rc = st.place()) != PMI_OK) return rc;
     // the histogram stays on the device: fill, then blur, on one stream
-    if ((rc = pmi_render_hist_dev(dx, dy, N, oversampling, y_min, x_min, y_max, x_max, (float *)d_hist, ny, nx, dn, nullptr)) != PMI_OK) return rc;
-    if ((rc = pmi_blur_dev((const float *)d_hist, (float *)d_out, ny, nx, d_wy, ry, d_wx, rx, round_between, scale, nullptr)) != PMI_OK) return rc;
-    PMI_HIP(hipMemcpy(image, d_out, (size_t)ny * nx * 4, hipMemcpyDeviceToHost));
-    PMI_HIP(hipMemcpy(n_rendered, dn, 8, hipMemcpyDeviceToHost));
-    return PMI_OK;
+    if ((rc = pmi_render_hist_dev(dx, dy, N, oversampling, y_min, x_min, y_max, x_max, d_hist, ny, nx, dn, nullptr)) != PMI_OK) return rc;
+    rc = pmi_blur_dev(d_hist, d_out, ny, nx, d_wy, ry, d_wx, rx, round_between, scale, nullptr);
+    return rc != PMI_OK ? rc : st.fetch();
 }
 
 }  // extern "C"

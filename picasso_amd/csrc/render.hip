@@ -22,6 +22,9 @@
 //      with an inf or NaN profile value (inf * 0 = NaN) is added inside its footprint only.
 // The result is the reference's image bit for bit, up to a 1-ulp difference between the
 // device's and glibc's float64 exp surviving the rounding to float32.
+// This file keeps its three kernels and its argument checks; the driver around them (scratch,
+// empty table, empty view, tile lists), the staging of the host forms and the table of scratch
+// slots are render_common.h's.
 #include "render_common.h"
 
 #pragma clang fp contract(off)
@@ -52,8 +55,7 @@ __global__ void hist_kernel(const float *__restrict__ x, const float *__restrict
         const int32_t yi = to_int32(v.oversampling * ((double)y[i] - v.y_min));
         atomicAdd(&image[(int64_t)yi * v.nx + xi], 1.0f);
     }
-    const unsigned long long bal = __ballot(ok);
-    if ((threadIdx.x & 63) == 0 && bal) atomicAdd(n_rendered, (unsigned long long)__popcll(bal));
+    count_in_view(ok, n_rendered);
 }
 
 // footprint of picasso/render.py:505-524, including its asymmetric "+ 1"
@@ -74,23 +76,15 @@ __global__ void prep_kernel(const float *__restrict__ x, const float *__restrict
             L.sy = v.os_f * np_maxf(lpy[i], v.min_blur_f);
             if (v.iso) { L.sy = (L.sy + L.sx) / 2.0f; L.sx = L.sy; }
             const double max_y_off = 3.0 * (double)L.sy, max_x_off = 3.0 * (double)L.sx;
-            int64_t i_min = to_int32(L.y - max_y_off);
-            if (i_min < 0) i_min = 0;
-            int64_t i_max = to_int32(L.y + max_y_off + 1);
-            if (i_max > v.ny) i_max = v.ny;
-            int64_t j_min = to_int32(L.x - max_x_off);
-            if (j_min < 0) j_min = 0;
-            int64_t j_max = (int64_t)to_int32(L.x + max_x_off) + 1;
-            if (j_max > v.nx) j_max = v.nx;
-            L.i_min = (int)i_min; L.i_max = (int)i_max; L.j_min = (int)j_min; L.j_max = (int)j_max;
-            if (i_max > i_min && j_max > j_min)
-                cnt = (unsigned)(((i_max - 1) / TILE - i_min / TILE + 1) * ((j_max - 1) / TILE - j_min / TILE + 1));
+            int64_t i_min = to_int32(L.y - max_y_off), i_max = to_int32(L.y + max_y_off + 1);
+            int64_t j_min = to_int32(L.x - max_x_off), j_max = (int64_t)to_int32(L.x + max_x_off) + 1;
+            cnt = clamp_footprint(v, i_min, i_max, j_min, j_max);
+            L.i_min = (int)i_min; L.i_max = (int)i_max; L.j_min = (int)j_min; L.j_max = (int)j_max;      // also when it is empty
         }
         locs[i] = L;
         ntiles[i] = cnt;
     }
-    const unsigned long long bal = __ballot(ok);
-    if ((threadIdx.x & 63) == 0 && bal) atomicAdd(n_rendered, (unsigned long long)__popcll(bal));
+    count_in_view(ok, n_rendered);
 }
 
 __global__ __launch_bounds__(256) void tile_kernel(const Loc *__restrict__ locs, const unsigned *__restrict__ vals,
@@ -185,8 +179,7 @@ extern "C" {
 int pmi_render_dims(double oversampling, double y_min, double x_min, double y_max, double x_max, int64_t *ny, int64_t *nx)
 {
     if (!ny || !nx) { pmi::set_error("null pointer"); return PMI_ERR_ARG; }
-    *ny = (int64_t)std::ceil(oversampling * (y_max - y_min));
-    *nx = (int64_t)std::ceil(oversampling * (x_max - x_min));
+    pmi::rend::view_dims(oversampling, y_min, x_min, y_max, x_max, ny, nx);
     return PMI_OK;
 }
 
@@ -201,11 +194,7 @@ int pmi_render_hist_dev(const float *d_x, const float *d_y, int64_t N, double ov
     hipStream_t s = (hipStream_t)stream;
     PMI_HIP(hipMemsetAsync(d_image, 0, (size_t)ny * nx * sizeof(float), s));
     PMI_HIP(hipMemsetAsync(d_n_rendered, 0, 8, s));
-    if (N > 0) {
-        hipLaunchKernelGGL(rend::hist_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, d_x, d_y, N, v, d_image,
-                           (unsigned long long *)d_n_rendered);
-        PMI_HIP(hipGetLastError());
-    }
+    if (N > 0) PMI_LAUNCH(rend::hist_kernel, N, s, d_x, d_y, N, v, d_image, (unsigned long long *)d_n_rendered);
     return PMI_OK;
 }
 
@@ -221,35 +210,13 @@ int pmi_render_gaussian_dev(const float *d_x, const float *d_y, const float *d_l
     v.iso = iso ? 1 : 0;
     if (N > 0x7fffffffLL) { set_error("render: too many localizations"); return PMI_ERR_ARG; }
     hipStream_t s = (hipStream_t)stream;
-    PMI_HIP(hipMemsetAsync(d_n_rendered, 0, 8, s));
-    const int64_t ntile = (int64_t)v.tiles_x * v.tiles_y;
-    if (N == 0) { PMI_HIP(hipMemsetAsync(d_image, 0, (size_t)ny * nx * sizeof(float), s)); return PMI_OK; }
-
-    // scratch: Loc[N], ntiles[N], offset[N], tile start/end
-    void *p_loc = nullptr, *p_cnt = nullptr, *p_tile = nullptr;
-    if ((rc = scratch(SCR_STAGE_B, (size_t)N * sizeof(rend::Loc), &p_loc)) != PMI_OK) return rc;
-    if ((rc = scratch(SCR_STAGE_C, (size_t)N * 8 + 64, &p_cnt)) != PMI_OK) return rc;
-    if ((rc = scratch(SCR_FRAME_COUNT, (size_t)ntile * 8, &p_tile)) != PMI_OK) return rc;
-    rend::Loc *locs = (rend::Loc *)p_loc;
-    unsigned *ntiles = (unsigned *)p_cnt, *offset = ntiles + N;
-    unsigned *start = (unsigned *)p_tile, *end = start + ntile;
-    const unsigned nb = (unsigned)((N + 255) / 256);
-    hipLaunchKernelGGL(rend::prep_kernel, dim3(nb), dim3(256), 0, s, d_x, d_y, d_lpx, d_lpy, N, v, locs, ntiles,
-                       (unsigned long long *)d_n_rendered);
-    PMI_HIP(hipGetLastError());
-
-    uint64_t E = 0;
-    unsigned *vals2 = nullptr;
-    if ((rc = rend::tile_lists(locs, ntiles, offset, N, v, start, &E, &vals2, s)) != PMI_OK) return rc;
-    if (E > 0) {
-        hipLaunchKernelGGL(rend::tile_kernel, dim3((unsigned)ntile), dim3(256), 0, s, locs, vals2, start, end, v, d_image);
-    } else {
-        PMI_HIP(hipMemsetAsync(d_image, 0, (size_t)ny * nx * sizeof(float), s));
-    }
-    PMI_HIP(hipGetLastError());
-    return PMI_OK;
+    return rend::gaussian<rend::Loc>(N, v, d_image, d_n_rendered, s, [&](rend::Loc *locs, unsigned *ntiles, unsigned long long *n_rendered) {
+        PMI_LAUNCH(rend::prep_kernel, N, s, d_x, d_y, d_lpx, d_lpy, N, v, locs, ntiles, n_rendered);
+        return (int)PMI_OK;
+    }, rend::tile_kernel);
 }
 
+// Host forms: columns, image and count are staged in the library's scratch (render_common.h), the results copied back.
 static int render_host(const float *x, const float *y, const float *lpx, const float *lpy, int64_t N, double oversampling,
                        double y_min, double x_min, double y_max, double x_max, double min_blur_width, int iso, bool gaussian,
                        float *image, int64_t ny, int64_t nx, int64_t *n_rendered)
@@ -257,29 +224,18 @@ static int render_host(const float *x, const float *y, const float *lpx, const f
     using namespace pmi;
     if (pmi_device_count() < 1) { set_error("no HIP device"); return PMI_ERR_NODEVICE; }
     if (!image || !n_rendered || (N > 0 && (!x || !y || (gaussian && (!lpx || !lpy))))) { set_error("null pointer"); return PMI_ERR_ARG; }
-    void *d_in = nullptr, *d_img = nullptr;
-    int rc;
-    const size_t col = (size_t)std::max<int64_t>(N, 1) * 4;
-    if ((rc = scratch(SCR_STAGE_A, col * 4 + 64, &d_in)) != PMI_OK) return rc;
-    const size_t img_bytes = (((size_t)ny * nx * 4 + 7) / 8) * 8;
-    if ((rc = scratch(SCR_IDS, img_bytes + 8, &d_img)) != PMI_OK) return rc;
-    float *dx = (float *)d_in, *dy = dx + N, *dlx = dy + N, *dly = dlx + N;
-    int64_t *dn = (int64_t *)((char *)d_img + img_bytes);
-    if (N > 0) {
-        PMI_HIP(hipMemcpy(dx, x, (size_t)N * 4, hipMemcpyHostToDevice));
-        PMI_HIP(hipMemcpy(dy, y, (size_t)N * 4, hipMemcpyHostToDevice));
-        if (gaussian) {
-            PMI_HIP(hipMemcpy(dlx, lpx, (size_t)N * 4, hipMemcpyHostToDevice));
-            PMI_HIP(hipMemcpy(dly, lpy, (size_t)N * 4, hipMemcpyHostToDevice));
-        }
-    }
-    rc = gaussian ? pmi_render_gaussian_dev(dx, dy, dlx, dly, N, oversampling, y_min, x_min, y_max, x_max, min_blur_width, iso,
-                                            (float *)d_img, ny, nx, dn, nullptr)
-                  : pmi_render_hist_dev(dx, dy, N, oversampling, y_min, x_min, y_max, x_max, (float *)d_img, ny, nx, dn, nullptr);
+    float *dx = nullptr, *dy = nullptr, *dlx = nullptr, *dly = nullptr, *d_img = nullptr;
+    int64_t *dn = nullptr;
+    const size_t n = (size_t)std::max<int64_t>(N, 0);
+    rend::Staged st;
+    st.add(dx, n, x), st.add(dy, n, y), st.add(dlx, n, lpx), st.add(dly, n, lpy);
+    st.add(d_img, (size_t)ny * nx, nullptr, image), st.add(dn, 1, nullptr, n_rendered);
+    int rc = st.place();
     if (rc != PMI_OK) return rc;
-    PMI_HIP(hipMemcpy(image, d_img, (size_t)ny * nx * 4, hipMemcpyDeviceToHost));
-    PMI_HIP(hipMemcpy(n_rendered, dn, 8, hipMemcpyDeviceToHost));
-    return PMI_OK;
+    rc = gaussian ? pmi_render_gaussian_dev(dx, dy, dlx, dly, N, oversampling, y_min, x_min, y_max, x_max, min_blur_width, iso,
+                                            d_img, ny, nx, dn, nullptr)
+                  : pmi_render_hist_dev(dx, dy, N, oversampling, y_min, x_min, y_max, x_max, d_img, ny, nx, dn, nullptr);
+    return rc != PMI_OK ? rc : st.fetch();
 }
 
 int pmi_render_hist(const float *x, const float *y, int64_t N, double oversampling, double y_min, double x_min,

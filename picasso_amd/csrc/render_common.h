@@ -1,17 +1,28 @@
-// render_common.h — what the Gaussian renders share (render.hip: flat view, render_rot.hip: rotated view): the viewport,
-// the reference's float -> integer conversions, and the tile schedule behind each one's own prep kernel:
-//   exclusive scan of the per-localization tile counts, emit (tile, localization) pairs in localization order, stable
-//   radix sort by tile -> every 32x32 tile gets its localizations in table order, then each tile's [start, end).
+// render_common.h — what the image kernels share (render.hip: flat view, render_rot.hip: rotated view, blur.hip: the
+// image blur): the viewport and the image-size limits, the reference's float -> integer conversions, the clamp and the
+// count every prep kernel ends on, the staging of a host form, and the Gaussian driver with its tile schedule:
+//   prep (each view's own kernel), exclusive scan of the per-localization tile counts, emit (tile, localization) pairs in
+//   localization order, stable radix sort by tile -> every 32x32 tile gets its localizations in table order, then each
+//   tile's [start, end), then the view's own tile kernel.
 // A localization record is any struct with the clipped footprint i_min, i_max, j_min, j_max ([min, max), ints).
+//
+// Scratch slots of the image layer.  A slot that grows is freed, so a pointer into it taken before is stale: a host form
+// and every _dev form it calls carve from disjoint slots, each with ONE rows::carve.
+//   SCR_STAGE_A   host forms (Staged): pmi_render_hist / _gaussian, pmi_rotate_locs, pmi_render_hist_rot / _gaussian_rot,
+//                 pmi_blur, pmi_render_blurred; pmi_radial_sum's image; pmi_frc_curve_dev's two float64 images
+//   SCR_STAGE_B   rocPRIM temporaries (rows::two_pass) — so no arena of this layer; pmi_frc_curve_dev's spectra (it sorts
+//                 and scans nothing)
+//   SCR_STAGE_C   gaussian(): records, tile counts, offsets, tile bounds; pmi_frc_curve and pmi_radial_sum (host forms
+//                 that call no _dev form of this file)
+//   SCR_STAGE_D   pmi_blur_dev: the image between the two passes
+//   SCR_RECORDS   tile_lists: the (tile, localization) pairs, unsorted and sorted
+// The histogram _dev forms and pmi_rotate_locs_dev take no scratch.
 #pragma once
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-
-#include "pmi_common.h"
+#include "rows_common.h"
 
 #pragma clang fp contract(off)
 
@@ -44,6 +55,24 @@ __device__ __forceinline__ int64_t to_int64(double v)
     return (v != v || v >= 9223372036854775808.0 || v < -9223372036854775808.0) ? (int64_t)0x8000000000000000LL : (int64_t)v;
 }
 
+// the four bounds as a view converts them, clamped to the image -> the tiles the footprint touches, 0 when it is empty
+__device__ __forceinline__ unsigned clamp_footprint(const View &v, int64_t &i_min, int64_t &i_max, int64_t &j_min, int64_t &j_max)
+{
+    if (i_min < 0) i_min = 0;
+    if (i_max > v.ny) i_max = v.ny;
+    if (j_min < 0) j_min = 0;
+    if (j_max > v.nx) j_max = v.nx;
+    if (i_max <= i_min || j_max <= j_min) return 0;
+    return (unsigned)(((i_max - 1) / TILE - i_min / TILE + 1) * ((j_max - 1) / TILE - j_min / TILE + 1));
+}
+
+// n_rendered += the lanes of the wave whose row is in view; every lane of the workgroup calls it
+__device__ __forceinline__ void count_in_view(bool ok, unsigned long long *n_rendered)
+{
+    const unsigned long long bal = __ballot(ok);
+    if ((threadIdx.x & 63) == 0 && bal) atomicAdd(n_rendered, (unsigned long long)__popcll(bal));
+}
+
 template <class L>
 __global__ void emit_kernel(const L *__restrict__ locs, const unsigned *__restrict__ ntiles,
                             const unsigned *__restrict__ offset, int64_t N, int tiles_x,
@@ -71,20 +100,64 @@ static __global__ void tile_bounds_kernel(const unsigned *__restrict__ keys, uns
     if (e + 1 == E || keys[e + 1] != k) end[k] = e + 1;
 }
 
+// (n_y, n_x) of a render (render.py:224-225)
+static void view_dims(double oversampling, double y_min, double x_min, double y_max, double x_max, int64_t *ny, int64_t *nx)
+{
+    *ny = (int64_t)std::ceil(oversampling * (y_max - y_min));
+    *nx = (int64_t)std::ceil(oversampling * (x_max - x_min));
+}
+
+// sides of 1 ... 2^31 - 1 and at most 2^31 - 1 tiles of 32 x 32 pixels; `what` heads the message
+static int check_image(const char *what, int64_t ny, int64_t nx)
+{
+    if (ny <= 0 || nx <= 0 || ny > 0x7fffffff || nx > 0x7fffffff) { set_error("%s: bad image size %lld x %lld", what, (long long)ny, (long long)nx); return PMI_ERR_ARG; }
+    if (((ny + TILE - 1) / TILE) * ((nx + TILE - 1) / TILE) > 0x7fffffffLL) { set_error("%s: image too large", what); return PMI_ERR_ARG; }
+    return PMI_OK;
+}
+
 static int make_view(double oversampling, double y_min, double x_min, double y_max, double x_max, double min_blur,
                      int64_t ny, int64_t nx, View *v)
 {
-    const int64_t ey = (int64_t)std::ceil(oversampling * (y_max - y_min));
-    const int64_t ex = (int64_t)std::ceil(oversampling * (x_max - x_min));
+    int64_t ey, ex;
+    view_dims(oversampling, y_min, x_min, y_max, x_max, &ey, &ex);
     if (ny != ey || nx != ex) { set_error("render: image is %lld x %lld but the viewport needs %lld x %lld", (long long)ny, (long long)nx, (long long)ey, (long long)ex); return PMI_ERR_ARG; }
-    if (ny <= 0 || nx <= 0 || ny > 0x7fffffff || nx > 0x7fffffff) { set_error("render: bad image size"); return PMI_ERR_ARG; }
+    const int rc = check_image("render", ny, nx);
+    if (rc != PMI_OK) return rc;
     v->oversampling = oversampling; v->y_min = y_min; v->x_min = x_min; v->y_max = y_max; v->x_max = x_max;
     v->os_f = (float)oversampling; v->min_blur_f = (float)min_blur; v->iso = 0;
     v->ny = ny; v->nx = nx;
     v->tiles_x = (int)((nx + TILE - 1) / TILE); v->tiles_y = (int)((ny + TILE - 1) / TILE);
-    if ((int64_t)v->tiles_x * v->tiles_y > 0x7fffffffLL) { set_error("render: image too large"); return PMI_ERR_ARG; }
     return PMI_OK;
 }
+
+// What a host form keeps on the device, in SCR_STAGE_A: every piece is named once, with the host array it is filled from
+// (`up`) or copied back to (`down`); place() carves them all and uploads, fetch() downloads.
+struct Staged {
+    struct Piece { void **dev; size_t bytes; const void *up; void *down; };
+    Piece pieces[12];
+    int n = 0;
+    template <typename T>
+    void add(T *&dev, size_t count, const void *up = nullptr, void *down = nullptr)
+    {
+        pieces[n++] = Piece{(void **)&dev, count * sizeof(T), up, down};
+    }
+    int place()
+    {
+        const int rc = rows::carve(SCR_STAGE_A, [&](rows::Arena &a) {
+            for (int k = 0; k < n; k++) *pieces[k].dev = a.take<char>(pieces[k].bytes);
+        });
+        if (rc != PMI_OK) return rc;
+        for (int k = 0; k < n; k++)
+            if (pieces[k].up && pieces[k].bytes) PMI_HIP(hipMemcpy(*pieces[k].dev, pieces[k].up, pieces[k].bytes, hipMemcpyHostToDevice));
+        return PMI_OK;
+    }
+    int fetch()
+    {
+        for (int k = 0; k < n; k++)
+            if (pieces[k].down && pieces[k].bytes) PMI_HIP(hipMemcpy(pieces[k].down, *pieces[k].dev, pieces[k].bytes, hipMemcpyDeviceToHost));
+        return PMI_OK;
+    }
+};
 
 // Behind a prep kernel that left locs[N] and ntiles[N] (offset: N entries; start: 2 * ntile entries, the second half
 // receives each tile's end): the tile lists.  Synchronises the stream once, the number of pairs *E sizes the sort buffers; with *E == 0 nothing is
@@ -95,14 +168,8 @@ static int tile_lists(const L *locs, const unsigned *ntiles, unsigned *offset, i
 {
     int rc;
     const int64_t ntile = (int64_t)v.tiles_x * v.tiles_y;
-    unsigned *end = start + ntile;
-    const unsigned nb = (unsigned)((N + 255) / 256);
     // exclusive scan -> offsets; the total decides the size of the pair buffers (one small D2H)
-    size_t tmp_bytes = 0;
-    PMI_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, ntiles, offset, 0u, (size_t)N, rocprim::plus<unsigned>(), s));
-    void *p_tmp = nullptr;
-    if ((rc = scratch(SCR_STAGE_D, tmp_bytes + 64, &p_tmp)) != PMI_OK) return rc;
-    PMI_HIP(rocprim::exclusive_scan(p_tmp, tmp_bytes, ntiles, offset, 0u, (size_t)N, rocprim::plus<unsigned>(), s));
+    if ((rc = rows::exclusive_scan_u32(ntiles, offset, (size_t)N, s)) != PMI_OK) return rc;
     unsigned last_off = 0, last_cnt = 0;
     PMI_HIP(hipMemcpyAsync(&last_off, offset + (N - 1), 4, hipMemcpyDeviceToHost, s));
     PMI_HIP(hipMemcpyAsync(&last_cnt, ntiles + (N - 1), 4, hipMemcpyDeviceToHost, s));
@@ -113,21 +180,43 @@ static int tile_lists(const L *locs, const unsigned *ntiles, unsigned *offset, i
 
     PMI_HIP(hipMemsetAsync(start, 0, (size_t)ntile * 8, s));
     if (E == 0) return PMI_OK;
-    void *p_pairs = nullptr;
-    if ((rc = scratch(SCR_RECORDS, (size_t)E * 16 + 64, &p_pairs)) != PMI_OK) return rc;
-    unsigned *keys = (unsigned *)p_pairs, *vals = keys + E, *keys2 = vals + E, *vals2 = keys2 + E;
-    hipLaunchKernelGGL(emit_kernel<L>, dim3(nb), dim3(256), 0, s, locs, ntiles, offset, N, v.tiles_x, keys, vals);
-    PMI_HIP(hipGetLastError());
-    int bits = 1;
-    while ((1LL << bits) < ntile) bits++;
-    size_t sort_bytes = 0;
-    PMI_HIP(rocprim::radix_sort_pairs(nullptr, sort_bytes, keys, keys2, vals, vals2, (size_t)E, 0, bits, s));
-    void *p_sort = nullptr;
-    if ((rc = scratch(SCR_RECORDS2, sort_bytes + 64, &p_sort)) != PMI_OK) return rc;
-    PMI_HIP(rocprim::radix_sort_pairs(p_sort, sort_bytes, keys, keys2, vals, vals2, (size_t)E, 0, bits, s));   // stable
-    hipLaunchKernelGGL(tile_bounds_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, s, keys2, (unsigned)E, start, end);
-    PMI_HIP(hipGetLastError());
+    unsigned *keys = nullptr, *vals = nullptr, *keys2 = nullptr, *vals2 = nullptr;
+    if ((rc = rows::carve(SCR_RECORDS, [&](rows::Arena &a) {
+             keys = a.take<unsigned>(E), vals = a.take<unsigned>(E), keys2 = a.take<unsigned>(E), vals2 = a.take<unsigned>(E);
+         })) != PMI_OK)
+        return rc;
+    PMI_LAUNCH(emit_kernel<L>, N, s, locs, ntiles, offset, N, v.tiles_x, keys, vals);
+    if ((rc = rows::sort_pairs(keys, keys2, vals, vals2, (size_t)E, rows::bits_of((uint64_t)ntile - 1), s)) != PMI_OK) return rc;   // stable
+    PMI_LAUNCH(tile_bounds_kernel, (int64_t)E, s, keys2, (unsigned)E, start, start + ntile);
     *vals_out = vals2;
+    return PMI_OK;
+}
+
+// The Gaussian render of either view behind its argument checks.  prep(locs, ntiles, n_rendered) launches the view's prep
+// kernel over the N rows; tile_kernel draws one tile from its list.  Synchronises the stream once (tile_lists).
+template <class L, class Prep, class TileKernel>
+static int gaussian(int64_t N, const View &v, float *d_image, int64_t *d_n_rendered, hipStream_t s, Prep &&prep, TileKernel tile_kernel)
+{
+    PMI_HIP(hipMemsetAsync(d_n_rendered, 0, 8, s));
+    const int64_t ntile = (int64_t)v.tiles_x * v.tiles_y;
+    const size_t image_bytes = (size_t)v.ny * v.nx * sizeof(float);
+    if (N == 0) { PMI_HIP(hipMemsetAsync(d_image, 0, image_bytes, s)); return PMI_OK; }
+    L *locs = nullptr;
+    unsigned *ntiles = nullptr, *offset = nullptr, *start = nullptr;
+    int rc = rows::carve(SCR_STAGE_C, [&](rows::Arena &a) {
+        locs = a.take<L>(N), ntiles = a.take<unsigned>(N), offset = a.take<unsigned>(N), start = a.take<unsigned>(2 * ntile);
+    });
+    if (rc != PMI_OK) return rc;
+    if ((rc = prep(locs, ntiles, (unsigned long long *)d_n_rendered)) != PMI_OK) return rc;
+    uint64_t E = 0;
+    unsigned *vals = nullptr;
+    if ((rc = tile_lists(locs, ntiles, offset, N, v, start, &E, &vals, s)) != PMI_OK) return rc;
+    if (E > 0) {
+        tile_kernel<<<(unsigned)ntile, 256, 0, s>>>(locs, vals, start, start + ntile, v, d_image);
+        PMI_HIP(hipGetLastError());
+    } else {
+        PMI_HIP(hipMemsetAsync(d_image, 0, image_bytes, s));
+    }
     return PMI_OK;
 }
 

@@ -32,6 +32,8 @@
 //      with glibc's exp (libm_glibc.h), the reference's under numba: the image is the reference's in every bit.
 //      A wave owns 8 whole rows of the tile and skips a record whose footprint misses them.
 // Contraction is off; the only fused operations are the ones written out above and those inside libm_glibc.h.
+// The driver around prep and tile kernel (rend::gaussian), the footprint clamp, the count of rows in view, the staging of
+// the host forms and the table of scratch slots are render_common.h's, shared with render.hip.
 #include "render_common.h"
 
 #include "libm_glibc.h"
@@ -121,8 +123,7 @@ __global__ void hist_rot_kernel(const T *__restrict__ x, const T *__restrict__ y
             if (xi >= 0 && yi >= 0 && xi < v.nx && yi < v.ny) atomicAdd(&image[(int64_t)yi * v.nx + xi], 1.0f);
         }
     }
-    const unsigned long long bal = __ballot(ok);
-    if ((threadIdx.x & 63) == 0 && bal) atomicAdd(n_rendered, (unsigned long long)__popcll(bal));
+    count_in_view(ok, n_rendered);
 }
 
 template <class T>
@@ -160,25 +161,18 @@ __global__ void prep_rot_kernel(const T *__restrict__ x, const T *__restrict__ y
                 L.m = inv01 + inv10;
                 L.norm = 1.0 / (6.283185307179586 * (double)sqrtf(det));
                 const double max_x_off = 3.0 * (double)sqrtf(s00), max_y_off = 3.0 * (double)sqrtf(s11);
-                int64_t j_min = to_int64(o.x - max_x_off);
-                if (j_min < 0) j_min = 0;
-                int64_t j_max = to_int64(o.x + max_x_off + 1);
-                if (j_max > v.nx) j_max = v.nx;
-                int64_t i_min = to_int64(o.y - max_y_off);
-                if (i_min < 0) i_min = 0;
-                int64_t i_max = to_int64(o.y + max_y_off + 1);
-                if (i_max > v.ny) i_max = v.ny;
-                if (i_max > i_min && j_max > j_min) {        // then 0 <= min < max <= the image side: all four fit an int
+                int64_t j_min = to_int64(o.x - max_x_off), j_max = to_int64(o.x + max_x_off + 1);
+                int64_t i_min = to_int64(o.y - max_y_off), i_max = to_int64(o.y + max_y_off + 1);
+                cnt = clamp_footprint(v, i_min, i_max, j_min, j_max);
+                if (cnt) {                                   // then 0 <= min < max <= the image side: all four fit an int
                     L.i_min = (int)i_min; L.i_max = (int)i_max; L.j_min = (int)j_min; L.j_max = (int)j_max;
-                    cnt = (unsigned)(((i_max - 1) / TILE - i_min / TILE + 1) * ((j_max - 1) / TILE - j_min / TILE + 1));
                 }
             }
         }
         locs[i] = L;
         ntiles[i] = cnt;
     }
-    const unsigned long long bal = __ballot(ok);
-    if ((threadIdx.x & 63) == 0 && bal) atomicAdd(n_rendered, (unsigned long long)__popcll(bal));
+    count_in_view(ok, n_rendered);
 }
 
 __global__ __launch_bounds__(256) void tile_rot_kernel(const RLoc *__restrict__ locs, const unsigned *__restrict__ vals,
@@ -264,14 +258,12 @@ int pmi_rotate_locs_dev(const void *d_x, const void *d_y, const void *d_z, int c
     if (N == 0) return PMI_OK;
     if (!d_x || !d_y || !d_z || !d_xr || !d_yr || !d_zr || !d_in_view) { set_error("null pointer"); return PMI_ERR_ARG; }
     hipStream_t s = (hipStream_t)stream;
-    const dim3 grid((unsigned)((N + 255) / 256));
     if (coords_f64)
-        hipLaunchKernelGGL(rend::rotate_kernel<double>, grid, dim3(256), 0, s, (const double *)d_x, (const double *)d_y,
-                           (const double *)d_z, N, v, R, d_xr, d_yr, d_zr, d_in_view);
+        PMI_LAUNCH(rend::rotate_kernel<double>, N, s, (const double *)d_x, (const double *)d_y, (const double *)d_z, N, v, R, d_xr,
+                   d_yr, d_zr, d_in_view);
     else
-        hipLaunchKernelGGL(rend::rotate_kernel<float>, grid, dim3(256), 0, s, (const float *)d_x, (const float *)d_y,
-                           (const float *)d_z, N, v, R, d_xr, d_yr, d_zr, d_in_view);
-    PMI_HIP(hipGetLastError());
+        PMI_LAUNCH(rend::rotate_kernel<float>, N, s, (const float *)d_x, (const float *)d_y, (const float *)d_z, N, v, R, d_xr,
+                   d_yr, d_zr, d_in_view);
     return PMI_OK;
 }
 
@@ -291,14 +283,12 @@ int pmi_render_hist_rot_dev(const void *d_x, const void *d_y, const void *d_z, i
     PMI_HIP(hipMemsetAsync(d_image, 0, (size_t)ny * nx * sizeof(float), s));
     PMI_HIP(hipMemsetAsync(d_n_rendered, 0, 8, s));
     if (N == 0) return PMI_OK;
-    const dim3 grid((unsigned)((N + 255) / 256));
     if (coords_f64)
-        hipLaunchKernelGGL(rend::hist_rot_kernel<double>, grid, dim3(256), 0, s, (const double *)d_x, (const double *)d_y,
-                           (const double *)d_z, N, v, R, d_image, (unsigned long long *)d_n_rendered);
+        PMI_LAUNCH(rend::hist_rot_kernel<double>, N, s, (const double *)d_x, (const double *)d_y, (const double *)d_z, N, v, R,
+                   d_image, (unsigned long long *)d_n_rendered);
     else
-        hipLaunchKernelGGL(rend::hist_rot_kernel<float>, grid, dim3(256), 0, s, (const float *)d_x, (const float *)d_y,
-                           (const float *)d_z, N, v, R, d_image, (unsigned long long *)d_n_rendered);
-    PMI_HIP(hipGetLastError());
+        PMI_LAUNCH(rend::hist_rot_kernel<float>, N, s, (const float *)d_x, (const float *)d_y, (const float *)d_z, N, v, R,
+                   d_image, (unsigned long long *)d_n_rendered);
     return PMI_OK;
 }
 
@@ -319,57 +309,26 @@ int pmi_render_gaussian_rot_dev(const void *d_x, const void *d_y, const void *d_
     if (N < 0 || N > 0x7fffffffLL) { set_error("render: too many localizations"); return PMI_ERR_ARG; }
     if (!d_image || !d_n_rendered || (N > 0 && (!d_x || !d_y || !d_z || !d_lpx || !d_lpy))) { set_error("null pointer"); return PMI_ERR_ARG; }
     hipStream_t s = (hipStream_t)stream;
-    PMI_HIP(hipMemsetAsync(d_n_rendered, 0, 8, s));
-    const int64_t ntile = (int64_t)v.tiles_x * v.tiles_y;
-    if (N == 0) { PMI_HIP(hipMemsetAsync(d_image, 0, (size_t)ny * nx * sizeof(float), s)); return PMI_OK; }
-
-    // scratch: RLoc[N], ntiles[N], offset[N], tile start/end
-    void *p_loc = nullptr, *p_cnt = nullptr, *p_tile = nullptr;
-    if ((rc = scratch(SCR_STAGE_B, (size_t)N * sizeof(rend::RLoc), &p_loc)) != PMI_OK) return rc;
-    if ((rc = scratch(SCR_STAGE_C, (size_t)N * 8 + 64, &p_cnt)) != PMI_OK) return rc;
-    if ((rc = scratch(SCR_FRAME_COUNT, (size_t)ntile * 8, &p_tile)) != PMI_OK) return rc;
-    rend::RLoc *locs = (rend::RLoc *)p_loc;
-    unsigned *ntiles = (unsigned *)p_cnt, *offset = ntiles + N;
-    unsigned *start = (unsigned *)p_tile, *end = start + ntile;
-    const dim3 grid((unsigned)((N + 255) / 256));
-    if (coords_f64)
-        hipLaunchKernelGGL(rend::prep_rot_kernel<double>, grid, dim3(256), 0, s, (const double *)d_x, (const double *)d_y,
-                           (const double *)d_z, d_lpx, d_lpy, d_lpz, N, v, R, locs, ntiles, (unsigned long long *)d_n_rendered);
-    else
-        hipLaunchKernelGGL(rend::prep_rot_kernel<float>, grid, dim3(256), 0, s, (const float *)d_x, (const float *)d_y,
-                           (const float *)d_z, d_lpx, d_lpy, d_lpz, N, v, R, locs, ntiles, (unsigned long long *)d_n_rendered);
-    PMI_HIP(hipGetLastError());
-    uint64_t E = 0;
-    unsigned *vals2 = nullptr;
-    if ((rc = rend::tile_lists(locs, ntiles, offset, N, v, start, &E, &vals2, s)) != PMI_OK) return rc;
-    if (E > 0) {
-        hipLaunchKernelGGL(rend::tile_rot_kernel, dim3((unsigned)ntile), dim3(256), 0, s, locs, vals2, start, end, v, d_image);
-    } else {
-        PMI_HIP(hipMemsetAsync(d_image, 0, (size_t)ny * nx * sizeof(float), s));
-    }
-    PMI_HIP(hipGetLastError());
-    return PMI_OK;
+    return rend::gaussian<rend::RLoc>(N, v, d_image, d_n_rendered, s, [&](rend::RLoc *locs, unsigned *ntiles, unsigned long long *n_rendered) {
+        if (coords_f64)
+            PMI_LAUNCH(rend::prep_rot_kernel<double>, N, s, (const double *)d_x, (const double *)d_y, (const double *)d_z, d_lpx,
+                       d_lpy, d_lpz, N, v, R, locs, ntiles, n_rendered);
+        else
+            PMI_LAUNCH(rend::prep_rot_kernel<float>, N, s, (const float *)d_x, (const float *)d_y, (const float *)d_z, d_lpx,
+                       d_lpy, d_lpz, N, v, R, locs, ntiles, n_rendered);
+        return (int)PMI_OK;
+    }, rend::tile_rot_kernel);
 }
 
-// Host forms: the columns are staged in the library's scratch, the results copied back.
-static int rot_stage(const void *x, const void *y, const void *z, int coords_f64, const float *lpx, const float *lpy,
-                     const float *lpz, int64_t N, char **d_cols)
+// Host forms: columns and results are staged in the library's scratch (render_common.h), the results copied back.
+// The coordinate columns of a rotated host form, of 4 or 8 bytes per value, named to `st`.
+static int rot_stage(pmi::rend::Staged &st, const void *x, const void *y, const void *z, int coords_f64, int64_t N, char *(&d)[3])
 {
     using namespace pmi;
     if (pmi_device_count() < 1) { set_error("no HIP device"); return PMI_ERR_NODEVICE; }
     if (N < 0 || (N > 0 && (!x || !y || !z))) { set_error("null pointer"); return PMI_ERR_ARG; }
-    const size_t es = coords_f64 ? 8 : 4, n = (size_t)std::max<int64_t>(N, 1);
-    void *d_in = nullptr;
-    int rc;
-    if ((rc = scratch(SCR_STAGE_A, n * (3 * es + 12) + 64, &d_in)) != PMI_OK) return rc;
-    char *p = (char *)d_in;
-    const void *coords[3] = {x, y, z};
-    const float *widths[3] = {lpx, lpy, lpz};
-    for (int k = 0; k < 3 && N > 0; k++) {
-        PMI_HIP(hipMemcpy(p + (size_t)k * N * es, coords[k], (size_t)N * es, hipMemcpyHostToDevice));
-        if (widths[k]) PMI_HIP(hipMemcpy(p + 3 * (size_t)N * es + (size_t)k * N * 4, widths[k], (size_t)N * 4, hipMemcpyHostToDevice));
-    }
-    *d_cols = p;
+    const size_t bytes = (size_t)N * (coords_f64 ? 8 : 4);
+    st.add(d[0], bytes, x), st.add(d[1], bytes, y), st.add(d[2], bytes, z);
     return PMI_OK;
 }
 
@@ -378,23 +337,18 @@ int pmi_rotate_locs(const void *x, const void *y, const void *z, int coords_f64,
                     double *zr, uint8_t *in_view)
 {
     using namespace pmi;
-    char *p = nullptr;
-    int rc = rot_stage(x, y, z, coords_f64, nullptr, nullptr, nullptr, N, &p);
+    rend::Staged st;
+    char *d[3] = {nullptr, nullptr, nullptr};
+    int rc = rot_stage(st, x, y, z, coords_f64, N, d);
     if (rc != PMI_OK) return rc;
     if (N > 0 && (!xr || !yr || !zr || !in_view)) { set_error("null pointer"); return PMI_ERR_ARG; }
-    const size_t es = coords_f64 ? 8 : 4, n = (size_t)std::max<int64_t>(N, 1);
-    void *d_out = nullptr;
-    if ((rc = scratch(SCR_IDS, n * 25 + 64, &d_out)) != PMI_OK) return rc;
-    double *dxr = (double *)d_out, *dyr = dxr + N, *dzr = dyr + N;
-    uint8_t *dv = (uint8_t *)(dzr + N);
-    rc = pmi_rotate_locs_dev(p, p + (size_t)N * es, p + 2 * (size_t)N * es, coords_f64, N, matrix, oversampling, y_min, x_min,
-                             y_max, x_max, dxr, dyr, dzr, dv, nullptr);
-    if (rc != PMI_OK || N == 0) return rc;
-    PMI_HIP(hipMemcpy(xr, dxr, (size_t)N * 8, hipMemcpyDeviceToHost));
-    PMI_HIP(hipMemcpy(yr, dyr, (size_t)N * 8, hipMemcpyDeviceToHost));
-    PMI_HIP(hipMemcpy(zr, dzr, (size_t)N * 8, hipMemcpyDeviceToHost));
-    PMI_HIP(hipMemcpy(in_view, dv, (size_t)N, hipMemcpyDeviceToHost));
-    return PMI_OK;
+    double *dxr = nullptr, *dyr = nullptr, *dzr = nullptr;
+    uint8_t *dv = nullptr;
+    st.add(dxr, N, nullptr, xr), st.add(dyr, N, nullptr, yr), st.add(dzr, N, nullptr, zr), st.add(dv, N, nullptr, in_view);
+    if ((rc = st.place()) != PMI_OK) return rc;
+    rc = pmi_rotate_locs_dev(d[0], d[1], d[2], coords_f64, N, matrix, oversampling, y_min, x_min, y_max, x_max, dxr, dyr, dzr, dv,
+                             nullptr);
+    return rc != PMI_OK ? rc : st.fetch();
 }
 
 static int render_rot_host(const void *x, const void *y, const void *z, int coords_f64, const float *lpx, const float *lpy,
@@ -404,26 +358,22 @@ static int render_rot_host(const void *x, const void *y, const void *z, int coor
 {
     using namespace pmi;
     if (!image || !n_rendered || (gaussian && N > 0 && (!lpx || !lpy))) { set_error("null pointer"); return PMI_ERR_ARG; }
-    if (ny <= 0 || nx <= 0) { set_error("render: bad image size"); return PMI_ERR_ARG; }
-    char *p = nullptr;
-    int rc = rot_stage(x, y, z, coords_f64, lpx, lpy, lpz, N, &p);
+    int rc = rend::check_image("render", ny, nx);
     if (rc != PMI_OK) return rc;
-    void *d_img = nullptr;
-    const size_t img_bytes = (((size_t)ny * nx * 4 + 7) / 8) * 8;
-    if ((rc = scratch(SCR_IDS, img_bytes + 8, &d_img)) != PMI_OK) return rc;
-    int64_t *dn = (int64_t *)((char *)d_img + img_bytes);
-    const size_t es = coords_f64 ? 8 : 4;
-    const char *dx = p, *dy = p + (size_t)N * es, *dz = p + 2 * (size_t)N * es;
-    const float *dl = (const float *)(p + 3 * (size_t)N * es);
-    rc = gaussian ? pmi_render_gaussian_rot_dev(dx, dy, dz, coords_f64, dl, dl + N, lpz ? dl + 2 * N : nullptr, N, matrix,
-                                                matrix_f32, oversampling, y_min, x_min, y_max, x_max, min_blur_width, iso,
-                                                (float *)d_img, ny, nx, dn, nullptr)
-                  : pmi_render_hist_rot_dev(dx, dy, dz, coords_f64, N, matrix, oversampling, y_min, x_min, y_max, x_max,
-                                            (float *)d_img, ny, nx, dn, nullptr);
-    if (rc != PMI_OK) return rc;
-    PMI_HIP(hipMemcpy(image, d_img, (size_t)ny * nx * 4, hipMemcpyDeviceToHost));
-    PMI_HIP(hipMemcpy(n_rendered, dn, 8, hipMemcpyDeviceToHost));
-    return PMI_OK;
+    rend::Staged st;
+    char *d[3] = {nullptr, nullptr, nullptr};
+    if ((rc = rot_stage(st, x, y, z, coords_f64, N, d)) != PMI_OK) return rc;
+    float *dlx = nullptr, *dly = nullptr, *dlz = nullptr, *d_img = nullptr;
+    int64_t *dn = nullptr;
+    st.add(dlx, N, lpx), st.add(dly, N, lpy);
+    if (lpz) st.add(dlz, N, lpz);
+    st.add(d_img, (size_t)ny * nx, nullptr, image), st.add(dn, 1, nullptr, n_rendered);
+    if ((rc = st.place()) != PMI_OK) return rc;
+    rc = gaussian ? pmi_render_gaussian_rot_dev(d[0], d[1], d[2], coords_f64, dlx, dly, dlz, N, matrix, matrix_f32, oversampling,
+                                                y_min, x_min, y_max, x_max, min_blur_width, iso, d_img, ny, nx, dn, nullptr)
+                  : pmi_render_hist_rot_dev(d[0], d[1], d[2], coords_f64, N, matrix, oversampling, y_min, x_min, y_max, x_max,
+                                            d_img, ny, nx, dn, nullptr);
+    return rc != PMI_OK ? rc : st.fetch();
 }
 
 int pmi_render_hist_rot(const void *x, const void *y, const void *z, int coords_f64, int64_t N, const double *matrix,

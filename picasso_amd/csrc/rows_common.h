@@ -2,7 +2,9 @@
 // scratch arena, the rocPRIM sorts and scan (and the two passes of any rocPRIM call), the argument checks of a row table
 // and the dispatch over the x / y element types.  Included by aim, link, cluster, knn, frc and fiducials directly; centers, kinetics, combine, areas and average through rows_groups.h, the
 // layer for tables ordered by a label column; pairs, picks and similar through rows_blocks.h, the layer for tables in
-// block order.  It pulls in rocPRIM: the fit kernels do not pay for it.
+// block order; render, render_rot and blur through render_common.h, the layer of the image kernels, which takes the arena,
+// the sort and the scan from here and keeps the table of its scratch slots.  It pulls in rocPRIM: the fit kernels do not
+// pay for it.
 #pragma once
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
