@@ -386,9 +386,21 @@ def xcorr_array(image_a, image_b) -> np.ndarray:
     return out
 
 
+def _roi_arg(roi) -> int:
+    """`roi` as the C calls take it: 0 for None (no crop), else the side of the centre crop.  The library reads 0 as
+    "no crop", while get_image_shift with roi=0 crops to nothing or to one row (picasso/imageprocess.py:89-101), so a
+    roi below 1 is refused here and never reaches the library as "no crop"."""
+    if roi is None:
+        return 0
+    if int(roi) < 1:
+        raise ValueError(f"roi must be None (no crop) or at least 1, got {roi!r}")
+    return int(roi)
+
+
 def rcc_pairs_arrays(segments, roi, box: int, pairs=None):
     """Pairs (i, j) of the segment images (all i < j when `pairs` is None) -> peak (n_pairs, 2),
     valid (n_pairs), fit windows (n_pairs, box, box) float64 and the crop offsets (Y_, X_)."""
+    roi = _roi_arg(roi)
     _lib.require_gpu()
     seg = np.ascontiguousarray(segments, np.float64)
     if seg.ndim != 3:
@@ -403,7 +415,7 @@ def rcc_pairs_arrays(segments, roi, box: int, pairs=None):
     rois = np.zeros((n_pairs, box, box), np.float64)
     crop = np.zeros(2, np.int32)
     with _lib.lock():
-        rc = _lib.load().pmi_rcc_pair_list(_lib.ptr(seg), n, Y, X, int(roi) if roi is not None else 0, int(box),
+        rc = _lib.load().pmi_rcc_pair_list(_lib.ptr(seg), n, Y, X, roi, int(box),
                                            _lib.ptr(pairs), n_pairs, _lib.ptr(peak), _lib.ptr(valid), _lib.ptr(rois),
                                            _lib.ptr(crop))
     _lib.check(rc, "pmi_rcc_pair_list")
@@ -429,6 +441,7 @@ def peak_fit_arrays(rois):
 def rcc_shifts_arrays(segments, roi, box: int, pairs=None):
     """get_image_shift (picasso/imageprocess.py:53-161) for pairs (i, j) of the segment images (all i < j when
     `pairs` is None), entirely on the device -> shifts (n_pairs, 2) = (-yc, -xc), fit status (n_pairs)."""
+    roi = _roi_arg(roi)
     _lib.require_gpu()
     seg = np.ascontiguousarray(segments, np.float64)
     if seg.ndim != 3:
@@ -441,7 +454,7 @@ def rcc_shifts_arrays(segments, roi, box: int, pairs=None):
     shifts = np.zeros((n_pairs, 2), np.float64)
     status = np.zeros(n_pairs, np.int32)
     with _lib.lock():
-        rc = _lib.load().pmi_rcc_shifts(_lib.ptr(seg), n, Y, X, int(roi) if roi is not None else 0, int(box), _lib.ptr(pairs),
+        rc = _lib.load().pmi_rcc_shifts(_lib.ptr(seg), n, Y, X, roi, int(box), _lib.ptr(pairs),
                                         n_pairs, _lib.ptr(shifts), _lib.ptr(status))
     _lib.check(rc, "pmi_rcc_shifts")
     return shifts, status
