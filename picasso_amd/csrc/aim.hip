@@ -483,31 +483,21 @@ int pmi_aim_roi_cc(int mode, const void *ref_x, const void *ref_y, const void *r
     }
     const bool zm = mode >= PMI_AIM_Z_F32;
     const size_t xy_b = (mode == PMI_AIM_XY_F32) ? 4 : 8, z_b = (mode == PMI_AIM_Z_F32) ? 4 : 8;
-    std::vector<void *> bufs;
-    struct Free { std::vector<void *> &b; ~Free() { for (void *p : b) (void)hipFree(p); } } fr{bufs};
-    auto up = [&](const void *h, int64_t cnt, size_t el, void **d) -> int {
-        *d = nullptr;
-        PMI_HIP(hipMalloc(d, std::max<size_t>(el * cnt, 1)));
-        bufs.push_back(*d);
-        if (h && cnt > 0) PMI_HIP(hipMemcpy(*d, h, el * cnt, hipMemcpyHostToDevice));
-        return PMI_OK;
-    };
-    void *drx, *dry, *drz = nullptr, *dx, *dy, *dz = nullptr, *dout;
-    if ((rc = up(ref_x, n_ref, xy_b, &drx)) || (rc = up(ref_y, n_ref, xy_b, &dry)) || (rc = up(x, n, xy_b, &dx)) ||
-        (rc = up(y, n, xy_b, &dy)))
-        return rc;
-    if (zm && ((rc = up(ref_z, n_ref, z_b, &drz)) || (rc = up(z, n, z_b, &dz)))) return rc;
-    if ((rc = up(nullptr, n_shifts + 1, sizeof(int32_t), &dout))) return rc;
+    // the six columns and the counts; a mode without z leaves drz and dz null
+    char *drx = nullptr, *dry = nullptr, *drz = nullptr, *dx = nullptr, *dy = nullptr, *dz = nullptr;
+    int32_t *dout = nullptr;
+    std::vector<int32_t> h(n_shifts + 1);
+    Staged st(SCR_STAGE_C);          // table_create carves SCR_STAGE_A and sorts through SCR_STAGE_B
+    st.add(drx, xy_b * n_ref, ref_x), st.add(dry, xy_b * n_ref, ref_y), st.add(dx, xy_b * n, x), st.add(dy, xy_b * n, y);
+    if (zm) st.add(drz, z_b * n_ref, ref_z), st.add(dz, z_b * n, z);
+    st.add(dout, h.size(), nullptr, h.data());
+    if ((rc = st.place())) return rc;
     aim::Table *t = nullptr;
     rc = aim::table_create(mode, aim::Cols{drx, dry, drz, nullptr, n_ref}, intersect_d, width_units, height_units,
                            shifts, n_shifts, &t, nullptr);
     if (rc) return rc;
-    rc = aim::count(t, aim::Cols{dx, dy, dz, nullptr, n}, rel_x, rel_y, rel_z, (int32_t *)dout, nullptr);
-    std::vector<int32_t> h(n_shifts + 1);
-    if (!rc) {
-        hipError_t e = hipMemcpy(h.data(), dout, sizeof(int32_t) * (n_shifts + 1), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy", __FILE__, __LINE__);
-    }
+    rc = aim::count(t, aim::Cols{dx, dy, dz, nullptr, n}, rel_x, rel_y, rel_z, dout, nullptr);
+    if (!rc) rc = st.fetch();
     aim::release(t);
     if (rc) return rc;
     if (h[n_shifts]) {

@@ -19,8 +19,8 @@
 // chunk's weights in LDS.  Every weight and every sample is staged once per workgroup and tile; the accumulators stay in
 // registers across chunks.  No atomics, no float32 accumulation, contraction off.
 //
-// The image limits (rend::check_image), the staging of the host forms (rend::Staged) and the table of scratch slots are
-// render_common.h's: pmi_blur_dev keeps the image between the passes in SCR_STAGE_D, the host forms everything in SCR_STAGE_A.
+// The image limits (rend::check_image) are render_common.h's, the staging of the host forms (Staged) and the table of
+// scratch slots pmi_common.h's: pmi_blur_dev keeps the image between the passes in SCR_STAGE_D, the host forms everything in SCR_STAGE_A.
 #include "render_common.h"
 
 #include "blur_core.h"
@@ -187,7 +187,7 @@ int pmi_blur_dev(const float *d_in, float *d_out, int64_t ny, int64_t nx, const 
 }
 
 // the weights of both axes named to `st`; a skipped axis has no piece and keeps its nullptr
-static int stage_weights(pmi::rend::Staged &st, const double *wy, int64_t ry, const double *wx, int64_t rx, double *&d_wy, double *&d_wx)
+static int stage_weights(pmi::Staged &st, const double *wy, int64_t ry, const double *wx, int64_t rx, double *&d_wy, double *&d_wx)
 {
     using namespace pmi;
     if ((wy && ry < 0) || (wx && rx < 0) || ry > 0x3fffffff || rx > 0x3fffffff) { set_error("blur: bad radius"); return PMI_ERR_ARG; }
@@ -206,7 +206,7 @@ int pmi_blur(const float *in, float *out, int64_t ny, int64_t nx, const double *
     if (rc != PMI_OK) return rc;
     float *d_in = nullptr, *d_out = nullptr;
     double *d_wy = nullptr, *d_wx = nullptr;
-    rend::Staged st;
+    Staged st(SCR_STAGE_A);
     st.add(d_in, (size_t)ny * nx, in), st.add(d_out, (size_t)ny * nx, nullptr, out);
     if ((rc = stage_weights(st, wy, ry, wx, rx, d_wy, d_wx)) != PMI_OK || (rc = st.place()) != PMI_OK) return rc;
     rc = pmi_blur_dev(d_in, d_out, ny, nx, d_wy, ry, d_wx, rx, round_between, scale, nullptr);
@@ -226,7 +226,7 @@ int pmi_render_blurred(const float *x, const float *y, int64_t N, double oversam
     double *d_wy = nullptr, *d_wx = nullptr;
     int64_t *dn = nullptr;
     const size_t n = (size_t)(N > 0 ? N : 0);
-    rend::Staged st;
+    Staged st(SCR_STAGE_A);
     st.add(dx, n, x), st.add(dy, n, y), st.add(d_hist, (size_t)ny * nx), st.add(dn, 1, nullptr, n_rendered);
     st.add(d_out, (size_t)ny * nx, nullptr, image);
     if ((rc = stage_weights(st, wy, ry, wx, rx, d_wy, d_wx)) != PMI_OK || (rc = st.place()) != PMI_OK) return rc;

@@ -216,21 +216,16 @@ int pmi_cumexp_fit(const double *values, int64_t n_values, const int64_t *offset
     }
     if (n_seg == 0) return PMI_OK;
     if (!offsets || !fit || !info || (n_values > 0 && !values)) { set_error("pmi_cumexp_fit: a NULL array"); return PMI_ERR_ARG; }
-    const size_t vb = (size_t)(n_values > 0 ? n_values : 1) * 8, ob = (size_t)(n_seg + 1) * 8;
-    const size_t fb = (size_t)n_seg * 4 * 8, ib = (size_t)n_seg * 2 * 4;
-    void *d_values = nullptr, *d_rest = nullptr;
+    double *d_values = nullptr, *d_fit = nullptr;
+    int64_t *d_offsets = nullptr;
+    int32_t *d_info = nullptr;
+    Staged st(SCR_STAGE_C);          // the _dev form carves SCR_STAGE_A and sorts through SCR_STAGE_B
+    st.add(d_values, n_values, values), st.add(d_offsets, (size_t)n_seg + 1, offsets);
+    st.add(d_fit, (size_t)n_seg * 4, nullptr, fit), st.add(d_info, (size_t)n_seg * 2, nullptr, info);
     int rc;
-    if ((rc = scratch(SCR_STAGE_C, vb + 64, &d_values)) != PMI_OK) return rc;
-    if ((rc = scratch(SCR_STAGE_D, ob + fb + ib + 64, &d_rest)) != PMI_OK) return rc;
-    int64_t *d_offsets = (int64_t *)d_rest;
-    double *d_fit = (double *)((char *)d_rest + ob);
-    int32_t *d_info = (int32_t *)((char *)d_rest + ob + fb);
-    if (n_values > 0) PMI_HIP(hipMemcpy(d_values, values, (size_t)n_values * 8, hipMemcpyHostToDevice));
-    PMI_HIP(hipMemcpy(d_offsets, offsets, ob, hipMemcpyHostToDevice));
-    if ((rc = pmi_cumexp_fit_dev((const double *)d_values, n_values, d_offsets, n_seg, kind, d_fit, d_info, nullptr)) != PMI_OK) return rc;
-    PMI_HIP(hipMemcpy(fit, d_fit, fb, hipMemcpyDeviceToHost));
-    PMI_HIP(hipMemcpy(info, d_info, ib, hipMemcpyDeviceToHost));
-    return PMI_OK;
+    if ((rc = st.place()) != PMI_OK) return rc;
+    if ((rc = pmi_cumexp_fit_dev(d_values, n_values, d_offsets, n_seg, kind, d_fit, d_info, nullptr)) != PMI_OK) return rc;
+    return st.fetch();
 }
 
 }  // extern "C"

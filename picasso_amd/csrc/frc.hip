@@ -230,21 +230,13 @@ int pmi_frc_curve(const float *im1, const float *im2, int64_t m, const double *w
     const int64_t mpix = m * m, npix = (int64_t)n * n;
     float *d_a = nullptr, *d_b = nullptr, *d_m1 = nullptr, *d_m2 = nullptr;
     double *d_w = nullptr, *d_sums = nullptr, *d_curve = nullptr;
-    if ((rc = rows::carve(SCR_STAGE_C, [&](rows::Arena &a) {
-             d_a = a.take<float>(mpix), d_b = a.take<float>(mpix), d_w = a.take<double>(n);
-             d_m1 = a.take<float>(npix), d_m2 = a.take<float>(npix);
-             d_sums = a.take<double>(3 * rings), d_curve = a.take<double>(rings);
-         })))
-        return rc;
-    PMI_HIP(hipMemcpy(d_a, im1, sizeof(float) * mpix, hipMemcpyHostToDevice));
-    PMI_HIP(hipMemcpy(d_b, im2, sizeof(float) * mpix, hipMemcpyHostToDevice));
-    PMI_HIP(hipMemcpy(d_w, w, sizeof(double) * n, hipMemcpyHostToDevice));
+    Staged st(SCR_STAGE_C);          // the _dev form carves SCR_STAGE_A and SCR_STAGE_B
+    st.add(d_a, mpix, im1), st.add(d_b, mpix, im2), st.add(d_w, n, w);
+    st.add(d_m1, npix, nullptr, masked1), st.add(d_m2, npix, nullptr, masked2);
+    st.add(d_sums, 3 * rings, nullptr, sums), st.add(d_curve, rings, nullptr, curve);
+    if ((rc = st.place())) return rc;
     if ((rc = pmi_frc_curve_dev(d_a, d_b, m, d_w, d_sums, d_curve, d_m1, d_m2, nullptr, nullptr))) return rc;
-    PMI_HIP(hipMemcpy(sums, d_sums, sizeof(double) * 3 * rings, hipMemcpyDeviceToHost));
-    PMI_HIP(hipMemcpy(curve, d_curve, sizeof(double) * rings, hipMemcpyDeviceToHost));
-    PMI_HIP(hipMemcpy(masked1, d_m1, sizeof(float) * npix, hipMemcpyDeviceToHost));
-    PMI_HIP(hipMemcpy(masked2, d_m2, sizeof(float) * npix, hipMemcpyDeviceToHost));
-    return PMI_OK;
+    return st.fetch();
 }
 
 int pmi_radial_sum(const void *image, int dtype, int64_t n, void *out)
@@ -258,10 +250,10 @@ int pmi_radial_sum(const void *image, int dtype, int64_t n, void *out)
     const size_t item = dtype == PMI_RADIAL_F32 ? 4 : dtype == PMI_RADIAL_C128 ? 16 : 8;
     const int64_t npix = n * n, rings = n / 2 + 1;
     char *d_image = nullptr, *d_out = nullptr;
-    int rc;
-    if ((rc = rows::carve(SCR_STAGE_A, [&](rows::Arena &a) { d_image = a.take<char>(item * npix); }))) return rc;
-    if ((rc = rows::carve(SCR_STAGE_C, [&](rows::Arena &a) { d_out = a.take<char>(item * rings); }))) return rc;
-    PMI_HIP(hipMemcpy(d_image, image, item * npix, hipMemcpyHostToDevice));
+    Staged st(SCR_STAGE_A);
+    st.add(d_image, item * npix, image), st.add(d_out, item * rings, nullptr, out);
+    const int rc = st.place();
+    if (rc) return rc;
     const unsigned grid = (unsigned)rings;
     const int32_t side = (int32_t)n;
     switch (dtype) {
@@ -271,8 +263,7 @@ int pmi_radial_sum(const void *image, int dtype, int64_t n, void *out)
     default: frc::radial_kernel<double, 2><<<grid, frc::BLOCK>>>((const double *)d_image, side, (double *)d_out); break;
     }
     PMI_HIP(hipGetLastError());
-    PMI_HIP(hipMemcpy(out, d_out, item * rings, hipMemcpyDeviceToHost));
-    return PMI_OK;
+    return st.fetch();
 }
 
 }  // extern "C"

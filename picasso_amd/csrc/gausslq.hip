@@ -964,19 +964,14 @@ int pmi_gausslq(const float *spots, int64_t N, int box, float *thetas, int32_t *
     if (rc != PMI_OK) return rc;
     if (N == 0) return PMI_OK;
     if (!spots || !thetas) { set_error("null pointer"); return PMI_ERR_ARG; }
-    void *d_in = nullptr, *d_out = nullptr;
-    const size_t in_bytes = (size_t)N * box * box * sizeof(float);
-    if ((rc = scratch(SCR_STAGE_A, in_bytes, &d_in)) != PMI_OK) return rc;
-    if ((rc = scratch(SCR_STAGE_B, (size_t)N * 8 * 4, &d_out)) != PMI_OK) return rc;
-    float *d_th = (float *)d_out;
-    int32_t *d_info = (int32_t *)(d_th + N * 6), *d_nfev = d_info + N;
-    PMI_HIP(hipMemcpy(d_in, spots, in_bytes, hipMemcpyHostToDevice));
-    rc = pmi_gausslq_dev((const float *)d_in, N, nullptr, box, d_th, d_info, d_nfev, nullptr);
-    if (rc != PMI_OK) return rc;
-    PMI_HIP(hipMemcpy(thetas, d_th, (size_t)N * 24, hipMemcpyDeviceToHost));
-    if (info) PMI_HIP(hipMemcpy(info, d_info, (size_t)N * 4, hipMemcpyDeviceToHost));
-    if (nfev) PMI_HIP(hipMemcpy(nfev, d_nfev, (size_t)N * 4, hipMemcpyDeviceToHost));
-    return PMI_OK;
+    float *d_sp = nullptr, *d_th = nullptr;
+    int32_t *d_info = nullptr, *d_nfev = nullptr;
+    Staged st(SCR_STAGE_A);
+    st.add(d_sp, (size_t)N * box * box, spots), st.add(d_th, (size_t)N * 6, nullptr, thetas);
+    st.add(d_info, N, nullptr, info), st.add(d_nfev, N, nullptr, nfev);        // info, nfev: optional
+    if ((rc = st.place()) != PMI_OK) return rc;
+    rc = pmi_gausslq_dev(d_sp, N, nullptr, box, d_th, d_info, d_nfev, nullptr);
+    return rc != PMI_OK ? rc : st.fetch();
 }
 
 int pmi_locs_from_fits_lq_dev(const int32_t *d_frame, const int32_t *d_y, const int32_t *d_x, const float *d_ng,

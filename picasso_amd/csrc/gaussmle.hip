@@ -979,21 +979,15 @@ int pmi_gaussmle(const float *spots, int64_t N, int box, double eps, int max_it,
     if (method != PMI_MLE_SIGMA && method != PMI_MLE_SIGMAXY) { set_error("Method not available."); return PMI_ERR_ARG; }
     if (N == 0) return PMI_OK;
     if (!spots || !thetas || !crlbs || !loglik || !iterations) { set_error("null pointer"); return PMI_ERR_ARG; }
-    void *d_in = nullptr, *d_out = nullptr;
+    float *d_sp = nullptr, *d_th = nullptr, *d_cr = nullptr, *d_ll = nullptr;
+    int32_t *d_it = nullptr;
+    Staged st(SCR_STAGE_A);
+    st.add(d_sp, (size_t)N * box * box, spots), st.add(d_th, (size_t)N * 6, nullptr, thetas), st.add(d_cr, (size_t)N * 6, nullptr, crlbs);
+    st.add(d_ll, N, nullptr, loglik), st.add(d_it, N, nullptr, iterations);
     int rc;
-    size_t in_bytes = (size_t)N * box * box * sizeof(float);
-    if ((rc = scratch(SCR_STAGE_A, in_bytes, &d_in)) != PMI_OK) return rc;
-    if ((rc = scratch(SCR_STAGE_B, (size_t)N * 14 * 4, &d_out)) != PMI_OK) return rc;
-    float *d_th = (float *)d_out, *d_cr = d_th + N * 6, *d_ll = d_cr + N * 6;
-    int32_t *d_it = (int32_t *)(d_ll + N);
-    PMI_HIP(hipMemcpy(d_in, spots, in_bytes, hipMemcpyHostToDevice));
-    rc = pmi_gaussmle_dev((const float *)d_in, N, nullptr, box, eps, max_it, method, d_th, d_cr, d_ll, d_it, nullptr);
-    if (rc != PMI_OK) return rc;
-    PMI_HIP(hipMemcpy(thetas, d_th, (size_t)N * 24, hipMemcpyDeviceToHost));
-    PMI_HIP(hipMemcpy(crlbs, d_cr, (size_t)N * 24, hipMemcpyDeviceToHost));
-    PMI_HIP(hipMemcpy(loglik, d_ll, (size_t)N * 4, hipMemcpyDeviceToHost));
-    PMI_HIP(hipMemcpy(iterations, d_it, (size_t)N * 4, hipMemcpyDeviceToHost));
-    return PMI_OK;
+    if ((rc = st.place()) != PMI_OK) return rc;
+    rc = pmi_gaussmle_dev(d_sp, N, nullptr, box, eps, max_it, method, d_th, d_cr, d_ll, d_it, nullptr);
+    return rc != PMI_OK ? rc : st.fetch();
 }
 
 int pmi_get_spots_dev(const void *d_movie, int dtype, int64_t F, int64_t Y, int64_t X, const int32_t *d_frame,
@@ -1033,12 +1027,15 @@ int pmi_get_spots(const void *movie, int dtype, int64_t F, int64_t Y, int64_t X,
         }
     const size_t frame_bytes = (size_t)Y * X * px_size(dtype);
     const int64_t chunk = std::max<int64_t>(1, (int64_t)((size_t)1 << 30) / (int64_t)frame_bytes);
-    void *d_chunk = nullptr, *d_ids = nullptr, *d_sp = nullptr;
+    // carved only: every run below fills and reads its own slices
+    char *d_chunk = nullptr;
+    int32_t *d_f = nullptr, *d_y = nullptr, *d_x = nullptr;
+    float *d_sp = nullptr;
+    Staged st(SCR_STAGE_A);
+    st.add(d_chunk, (size_t)std::min<int64_t>(chunk, F) * frame_bytes), st.add(d_f, N), st.add(d_y, N), st.add(d_x, N);
+    st.add(d_sp, (size_t)N * box * box);
     int rc;
-    if ((rc = scratch(SCR_STAGE_A, (size_t)std::min<int64_t>(chunk, F) * frame_bytes, &d_chunk)) != PMI_OK) return rc;
-    if ((rc = scratch(SCR_STAGE_B, (size_t)N * 12, &d_ids)) != PMI_OK) return rc;
-    if ((rc = scratch(SCR_STAGE_C, (size_t)N * box * box * 4, &d_sp)) != PMI_OK) return rc;
-    int32_t *d_f = (int32_t *)d_ids, *d_y = d_f + N, *d_x = d_y + N;
+    if ((rc = st.place()) != PMI_OK) return rc;
     // identifications are normally frame-sorted; process maximal runs that fit one chunk
     std::vector<int32_t> rel(N);
     int64_t i0 = 0;
@@ -1052,12 +1049,12 @@ int pmi_get_spots(const void *movie, int dtype, int64_t F, int64_t Y, int64_t X,
         int64_t cnt = i1 - i0, nfc = fmax - fmin + 1;
         for (int64_t i = i0; i < i1; i++) rel[i - i0] = (int32_t)(frame[i] - fmin);
         PMI_HIP(hipMemcpy(d_chunk, (const char *)movie + (size_t)fmin * frame_bytes, (size_t)nfc * frame_bytes, hipMemcpyHostToDevice));
-        PMI_HIP(hipMemcpy(d_f, rel.data(), (size_t)cnt * 4, hipMemcpyHostToDevice));
-        PMI_HIP(hipMemcpy(d_y, y + i0, (size_t)cnt * 4, hipMemcpyHostToDevice));
-        PMI_HIP(hipMemcpy(d_x, x + i0, (size_t)cnt * 4, hipMemcpyHostToDevice));
-        rc = pmi_get_spots_dev(d_chunk, dtype, nfc, Y, X, d_f, d_y, d_x, cnt, nullptr, box, baseline, sensitivity, gain, (float *)d_sp, nullptr);
+        PMI_HIP(hipMemcpy(d_f, rel.data(), (size_t)cnt * sizeof(int32_t), hipMemcpyHostToDevice));
+        PMI_HIP(hipMemcpy(d_y, y + i0, (size_t)cnt * sizeof(int32_t), hipMemcpyHostToDevice));
+        PMI_HIP(hipMemcpy(d_x, x + i0, (size_t)cnt * sizeof(int32_t), hipMemcpyHostToDevice));
+        rc = pmi_get_spots_dev(d_chunk, dtype, nfc, Y, X, d_f, d_y, d_x, cnt, nullptr, box, baseline, sensitivity, gain, d_sp, nullptr);
         if (rc != PMI_OK) return rc;
-        PMI_HIP(hipMemcpy(out_spots + (size_t)i0 * box * box, d_sp, (size_t)cnt * box * box * 4, hipMemcpyDeviceToHost));
+        PMI_HIP(hipMemcpy(out_spots + (size_t)i0 * box * box, d_sp, (size_t)cnt * box * box * sizeof(float), hipMemcpyDeviceToHost));
         i0 = i1;
     }
     return PMI_OK;

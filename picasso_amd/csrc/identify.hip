@@ -621,14 +621,17 @@ int pmi_identify(const void *movie, int dtype, int64_t F, int64_t Y, int64_t X, 
     if (f_hi < f_lo) return PMI_OK;
     const size_t frame_bytes = (size_t)Y * X * dtype_size(dtype);
     const int64_t chunk = std::max<int64_t>(1, (int64_t)((size_t)1 << 30) / (int64_t)frame_bytes);   // ~1 GiB of frames
-    void *d_chunk = nullptr, *ptr = nullptr;
+    // carved only: every chunk below fills the movie slice and reads back the rows it found
+    char *d_chunk = nullptr;
+    int32_t *d_frame = nullptr, *d_y = nullptr, *d_x = nullptr;
+    float *d_ng = nullptr;
+    int64_t *d_n = nullptr;
+    const size_t dcap = (size_t)std::max<int64_t>(cap, 1);
+    Staged st(SCR_STAGE_A);
+    st.add(d_chunk, (size_t)std::min<int64_t>(chunk, f_hi - f_lo + 1) * frame_bytes);
+    st.add(d_frame, dcap), st.add(d_y, dcap), st.add(d_x, dcap), st.add(d_ng, dcap), st.add(d_n, 1);
     int rc;
-    if ((rc = scratch(SCR_STAGE_A, (size_t)std::min<int64_t>(chunk, f_hi - f_lo + 1) * frame_bytes, &d_chunk)) != PMI_OK) return rc;
-    int64_t dcap = std::max<int64_t>(cap, 1);
-    if ((rc = scratch(SCR_STAGE_B, (size_t)dcap * 16 + 64, &ptr)) != PMI_OK) return rc;
-    int32_t *d_frame = (int32_t *)ptr, *d_y = d_frame + dcap, *d_x = d_y + dcap;
-    float *d_ng = (float *)(d_x + dcap);
-    int64_t *d_n = (int64_t *)(d_ng + dcap);
+    if ((rc = st.place()) != PMI_OK) return rc;
     int64_t total = 0;
     bool overflow = false;
     for (int64_t c0 = f_lo; c0 <= f_hi; c0 += chunk) {
@@ -642,10 +645,10 @@ int pmi_identify(const void *movie, int dtype, int64_t F, int64_t Y, int64_t X, 
         PMI_HIP(hipMemcpy(&n, d_n, sizeof(n), hipMemcpyDeviceToHost));
         if (n > room) overflow = true;
         else if (n > 0) {
-            PMI_HIP(hipMemcpy(out_frame + total, d_frame, (size_t)n * 4, hipMemcpyDeviceToHost));
-            PMI_HIP(hipMemcpy(out_y + total, d_y, (size_t)n * 4, hipMemcpyDeviceToHost));
-            PMI_HIP(hipMemcpy(out_x + total, d_x, (size_t)n * 4, hipMemcpyDeviceToHost));
-            PMI_HIP(hipMemcpy(out_ng + total, d_ng, (size_t)n * 4, hipMemcpyDeviceToHost));
+            PMI_HIP(hipMemcpy(out_frame + total, d_frame, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+            PMI_HIP(hipMemcpy(out_y + total, d_y, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+            PMI_HIP(hipMemcpy(out_x + total, d_x, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+            PMI_HIP(hipMemcpy(out_ng + total, d_ng, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
         }
         total += n;
     }
@@ -671,23 +674,18 @@ int pmi_net_gradient(const float *image, int64_t Y, int64_t X, const int32_t *y,
             set_error("net_gradient: position %lld (%d, %d) reaches outside the %lld x %lld image", (long long)i, y[i], x[i], (long long)Y, (long long)X);
             return PMI_ERR_ARG;
         }
-    void *pa = nullptr, *pb = nullptr;
-    int rc;
-    const size_t img_bytes = (size_t)Y * X * 4, tab = (size_t)box * box * 4;
-    if ((rc = scratch(SCR_STAGE_A, img_bytes, &pa)) != PMI_OK) return rc;
-    if ((rc = scratch(SCR_STAGE_B, (size_t)n * 12 + 2 * tab + 64, &pb)) != PMI_OK) return rc;
-    int32_t *d_y = (int32_t *)pb, *d_x = d_y + n;
-    float *d_out = (float *)(d_x + n), *d_uy = d_out + n, *d_ux = d_uy + box * box;
-    PMI_HIP(hipMemcpy(pa, image, img_bytes, hipMemcpyHostToDevice));
-    PMI_HIP(hipMemcpy(d_y, y, (size_t)n * 4, hipMemcpyHostToDevice));
-    PMI_HIP(hipMemcpy(d_x, x, (size_t)n * 4, hipMemcpyHostToDevice));
-    PMI_HIP(hipMemcpy(d_uy, uy, tab, hipMemcpyHostToDevice));
-    PMI_HIP(hipMemcpy(d_ux, ux, tab, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(net_gradient_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, (const float *)pa, (int)Y,
+    float *d_image = nullptr, *d_uy = nullptr, *d_ux = nullptr, *d_out = nullptr;
+    int32_t *d_y = nullptr, *d_x = nullptr;
+    const size_t tab = (size_t)box * box;
+    Staged st(SCR_STAGE_A);
+    st.add(d_image, (size_t)Y * X, image), st.add(d_y, n, y), st.add(d_x, n, x), st.add(d_uy, tab, uy), st.add(d_ux, tab, ux);
+    st.add(d_out, n, nullptr, out_ng);
+    const int rc = st.place();
+    if (rc != PMI_OK) return rc;
+    hipLaunchKernelGGL(net_gradient_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, (const float *)d_image, (int)Y,
                        (int)X, d_y, d_x, n, box, d_uy, d_ux, d_out);
     PMI_HIP(hipGetLastError());
-    PMI_HIP(hipMemcpy(out_ng, d_out, (size_t)n * 4, hipMemcpyDeviceToHost));
-    return PMI_OK;
+    return st.fetch();
 }
 
 }  // extern "C"

@@ -454,18 +454,16 @@ int rcc_fit_peaks(const double *d_rois, const int32_t *h_peaks3, int64_t n_pairs
                   int64_t X_, double *h_shift_yx, int32_t *h_status)
 {
     if (n_pairs <= 0) return PMI_OK;
-    void *ptr = nullptr;
-    int rc = scratch(SCR_FIT, (size_t)n_pairs * (3 * 4 + 2 * 8 + 4) + 64, &ptr);
+    double *d_shift = nullptr;
+    int32_t *d_peaks = nullptr, *d_status = nullptr;
+    Staged st(SCR_FIT);              // not the slot the windows at d_rois are resident in (rcc_pair_list_impl, xcorr.hip)
+    st.add(d_shift, (size_t)n_pairs * 2, nullptr, h_shift_yx), st.add(d_peaks, (size_t)n_pairs * 3, h_peaks3), st.add(d_status, n_pairs, nullptr, h_status);
+    const int rc = st.place();
     if (rc != PMI_OK) return rc;
-    double *d_shift = (double *)ptr;
-    int32_t *d_peaks = (int32_t *)(d_shift + 2 * n_pairs), *d_status = d_peaks + 3 * n_pairs;
-    PMI_HIP(hipMemcpy(d_peaks, h_peaks3, (size_t)n_pairs * 12, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(pk::peak_fit_kernel, dim3((unsigned)((n_pairs + pk::PK_WAVES - 1) / pk::PK_WAVES)), dim3(pk::PK_WAVES * 64), 0, 0, d_rois, d_peaks, n_pairs, box,
                        Y, X, Y_, X_, d_shift, (double *)nullptr, d_status);
     PMI_HIP(hipGetLastError());
-    PMI_HIP(hipMemcpy(h_shift_yx, d_shift, (size_t)n_pairs * 16, hipMemcpyDeviceToHost));
-    PMI_HIP(hipMemcpy(h_status, d_status, (size_t)n_pairs * 4, hipMemcpyDeviceToHost));
-    return PMI_OK;
+    return st.fetch();
 }
 
 }  // namespace pmi
@@ -479,22 +477,19 @@ int pmi_peak_fit(const double *rois, int64_t n, int box, double *popt, int32_t *
     if (pmi_device_count() < 1) { set_error("no HIP device"); return PMI_ERR_NODEVICE; }
     if (n == 0) return PMI_OK;
     if (!rois || !popt || !status || n < 0 || box < 3 || box > 15 || !(box & 1)) { set_error("peak fit: bad arguments"); return PMI_ERR_ARG; }
-    void *ptr = nullptr;
-    const size_t rb = (size_t)n * box * box * 8;
-    int rc = scratch(SCR_STAGE_D, rb + (size_t)n * (12 + 16 + 40 + 4) + 64, &ptr);
-    if (rc != PMI_OK) return rc;
-    double *d_rois = (double *)ptr, *d_shift = d_rois + (size_t)n * box * box, *d_popt = d_shift + 2 * n;
-    int32_t *d_peaks = (int32_t *)(d_popt + 5 * n), *d_status = d_peaks + 3 * n;
     std::vector<int32_t> pk3((size_t)n * 3, 0);
     for (int64_t i = 0; i < n; i++) pk3[(size_t)i * 3 + 2] = 1;
-    PMI_HIP(hipMemcpy(d_rois, rois, rb, hipMemcpyHostToDevice));
-    PMI_HIP(hipMemcpy(d_peaks, pk3.data(), (size_t)n * 12, hipMemcpyHostToDevice));
+    double *d_rois = nullptr, *d_shift = nullptr, *d_popt = nullptr;
+    int32_t *d_peaks = nullptr, *d_status = nullptr;
+    Staged st(SCR_STAGE_D);
+    st.add(d_rois, (size_t)n * box * box, rois), st.add(d_shift, (size_t)n * 2), st.add(d_popt, (size_t)n * PK_N, nullptr, popt);
+    st.add(d_peaks, pk3.size(), pk3.data()), st.add(d_status, n, nullptr, status);
+    const int rc = st.place();
+    if (rc != PMI_OK) return rc;
     hipLaunchKernelGGL(pk::peak_fit_kernel, dim3((unsigned)((n + pk::PK_WAVES - 1) / pk::PK_WAVES)), dim3(pk::PK_WAVES * 64), 0, 0, d_rois, d_peaks, n, box, (int64_t)0,
                        (int64_t)0, (int64_t)0, (int64_t)0, d_shift, d_popt, d_status);
     PMI_HIP(hipGetLastError());
-    PMI_HIP(hipMemcpy(popt, d_popt, (size_t)n * 40, hipMemcpyDeviceToHost));
-    PMI_HIP(hipMemcpy(status, d_status, (size_t)n * 4, hipMemcpyDeviceToHost));
-    return PMI_OK;
+    return st.fetch();
 }
 
 }  // extern "C"

@@ -42,6 +42,38 @@ int checked_device(int *device);      // the same with a status: PMI_ERR_HIP / P
 int device_cu_count();                // compute units of that device (cached per device)
 
 // Grow-only scratch arena per device.  slot = purpose id.
+//
+// The rule.  A slot that grows is freed, so a pointer into it taken before is stale.  Hence: ONE carve per slot per call
+// (scratch(), carve() or Staged::place()), and the slots of a host form are disjoint from those of every _dev form or
+// helper it calls.  Who carves from which slot (host forms stage through Staged, further down):
+//   SCR_STAGE_A   host  pmi_zfit, pmi_avgroi, pmi_gaussmle, pmi_get_spots, pmi_gausslq, pmi_identify, pmi_net_gradient,
+//                       pmi_xcorr, pmi_rcc_pair_list / pmi_rcc_pairs / pmi_rcc_shifts (rcc_pair_list_impl: the fit windows
+//                       stay resident here for rcc_fit_peaks), pmi_radial_sum, and the image layer's host forms
+//                       (render_common.h)
+//                 _dev  pmi_aim_partition_dev, pmi_aim_table_create_dev (aim::table_create), pmi_link_groups_dev,
+//                       pmi_link_combine_dev, pmi_nena_hist_dev, pmi_cluster_counts_dev / _smlm_dev / _dbscan_dev,
+//                       pmi_knn_order_dev, pmi_pairs_order_dev / _density_dev / _distance_hist_dev, pmi_picks_circle_dev /
+//                       _shape_dev, pmi_similar_shift_dev, pmi_centers_order_dev / _stats_dev / _hull_dev,
+//                       pmi_kinetics_dark_order_dev / _stats_dev, pmi_combine_order_dev / _stats_dev / _mindist_dev,
+//                       pmi_fiducials_drift_dev, pmi_cumexp_fit_dev, pmi_frc_curve_dev
+//   SCR_STAGE_B   host  none
+//                 _dev  every rocPRIM temporary (rows::two_pass: the sorts and scans of the row, group, block and image
+//                       layers, pmi_cumexp_fit_dev's segmented sort) and pmi_frc_curve_dev's spectra (it sorts nothing)
+//   SCR_STAGE_C   host  pmi_cumexp_fit, pmi_frc_curve, pmi_aim_roi_cc
+//                 _dev  the cut spots of a fit from the movie (fit_impl: pmi_gaussmle_movie_dev, pmi_localize_mle_dev;
+//                       lq::launch: pmi_gausslq_movie_dev, pmi_localize_lq_dev), pmi_cluster_smlm_dev and
+//                       pmi_cluster_frame_analysis_dev, the Gaussian renders (render_common.h)
+//   SCR_STAGE_D   host  pmi_peak_fit
+//                 _dev  the work arrays of every MLE and least-squares fit (fit_impl, lq::launch), pmi_blur_dev
+//   SCR_FIT       host  pmi_rcc_shifts (rcc_fit_peaks, behind rcc_pair_list_impl's SCR_STAGE_A)
+//                 _dev  every MLE fit (fit_impl)
+//   SCR_RECORDS, SCR_RECORDS2, SCR_FRAME_COUNT, SCR_COUNTERS, SCR_NARROW, SCR_GATES
+//                 _dev  identify_impl: pmi_identify_dev, every chunk of pmi_identify, the fused calls; SCR_RECORDS also the
+//                       tile lists of the Gaussian renders (render_common.h)
+//   SCR_IDS, SCR_ROWS, SCR_DEFER_PRIOR
+//                 _dev  the fused calls pmi_localize_mle_dev and pmi_localize_lq_dev (fused_ranges, defer_prior_begin)
+//   SCR_STATS, SCR_LQ_STATS
+//                 _dev  every MLE fit and every least-squares fit: the 64 bytes LastFitStats reads later
 enum ScratchSlot {
     SCR_RECORDS = 0,      // unordered identification records
     SCR_RECORDS2,         // frame-grouped records
@@ -62,6 +94,69 @@ enum ScratchSlot {
     SCR_NUM
 };
 int scratch(int slot, size_t bytes, void **ptr);
+
+// one scratch slot cut into 256-byte aligned pieces; without a base it only measures
+struct Arena {
+    char *base = nullptr;
+    size_t used = 0;
+    template <typename T>
+    T *take(size_t count)
+    {
+        T *p = base ? (T *)(base + used) : nullptr;
+        used += (count * sizeof(T) + 255) & ~size_t(255);
+        return p;
+    }
+};
+
+// layout(Arena &) takes every piece of a call, in one order: it runs once to measure and once on the slot's buffer,
+// so the size asked for is the size used.  The pieces start at the first one taken and span *used bytes.
+template <typename Layout>
+static int carve(int slot, Layout &&layout, size_t *used = nullptr)
+{
+    Arena measure;
+    layout(measure);
+    void *base = nullptr;
+    const int rc = scratch(slot, measure.used, &base);
+    if (rc != PMI_OK) return rc;
+    Arena place;
+    place.base = (char *)base;
+    layout(place);
+    if (used) *used = place.used;
+    return PMI_OK;
+}
+
+// What a host form keeps on the device, in one slot: every piece is named once, with the host array it is filled from
+// (`up`) or copied back to (`down`), or with neither (a work buffer); place() carves them all and uploads, fetch()
+// downloads.  A piece of zero bytes is carved and never copied.
+struct Staged {
+    struct Piece { void **dev; size_t bytes; const void *up; void *down; };
+    Piece pieces[12];
+    int n = 0;
+    const int slot;
+    explicit Staged(int slot_) : slot(slot_) {}
+    template <typename T>
+    void add(T *&dev, size_t count, const void *up = nullptr, void *down = nullptr)
+    {
+        pieces[n++] = Piece{(void **)&dev, count * sizeof(T), up, down};
+    }
+    int place()
+    {
+        const int rc = carve(slot, [&](Arena &a) {
+            for (int k = 0; k < n; k++) *pieces[k].dev = a.take<char>(pieces[k].bytes);
+        });
+        if (rc != PMI_OK) return rc;
+        for (int k = 0; k < n; k++)
+            if (pieces[k].up && pieces[k].bytes) PMI_HIP(hipMemcpy(*pieces[k].dev, pieces[k].up, pieces[k].bytes, hipMemcpyHostToDevice));
+        return PMI_OK;
+    }
+    int fetch()
+    {
+        for (int k = 0; k < n; k++)
+            if (pieces[k].down && pieces[k].bytes) PMI_HIP(hipMemcpy(pieces[k].down, *pieces[k].dev, pieces[k].bytes, hipMemcpyDeviceToHost));
+        return PMI_OK;
+    }
+};
+
 int scratch_release_all();
 int scratch_enter_inner();           // -> the bank to hand back to scratch_leave_inner
 void scratch_leave_inner(int was);

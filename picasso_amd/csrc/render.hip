@@ -216,7 +216,7 @@ int pmi_render_gaussian_dev(const float *d_x, const float *d_y, const float *d_l
     }, rend::tile_kernel);
 }
 
-// Host forms: columns, image and count are staged in the library's scratch (render_common.h), the results copied back.
+// Host forms: columns, image and count are staged in the library's scratch (Staged, pmi_common.h), the results copied back.
 static int render_host(const float *x, const float *y, const float *lpx, const float *lpy, int64_t N, double oversampling,
                        double y_min, double x_min, double y_max, double x_max, double min_blur_width, int iso, bool gaussian,
                        float *image, int64_t ny, int64_t nx, int64_t *n_rendered)
@@ -227,7 +227,7 @@ static int render_host(const float *x, const float *y, const float *lpx, const f
     float *dx = nullptr, *dy = nullptr, *dlx = nullptr, *dly = nullptr, *d_img = nullptr;
     int64_t *dn = nullptr;
     const size_t n = (size_t)std::max<int64_t>(N, 0);
-    rend::Staged st;
+    Staged st(SCR_STAGE_A);
     st.add(dx, n, x), st.add(dy, n, y), st.add(dlx, n, lpx), st.add(dly, n, lpy);
     st.add(d_img, (size_t)ny * nx, nullptr, image), st.add(dn, 1, nullptr, n_rendered);
     int rc = st.place();

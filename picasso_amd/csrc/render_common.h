@@ -1,19 +1,16 @@
 // render_common.h — what the image kernels share (render.hip: flat view, render_rot.hip: rotated view, blur.hip: the
 // image blur): the viewport and the image-size limits, the reference's float -> integer conversions, the clamp and the
-// count every prep kernel ends on, the staging of a host form, and the Gaussian driver with its tile schedule:
+// count every prep kernel ends on, and the Gaussian driver with its tile schedule:
 //   prep (each view's own kernel), exclusive scan of the per-localization tile counts, emit (tile, localization) pairs in
 //   localization order, stable radix sort by tile -> every 32x32 tile gets its localizations in table order, then each
 //   tile's [start, end), then the view's own tile kernel.
 // A localization record is any struct with the clipped footprint i_min, i_max, j_min, j_max ([min, max), ints).
 //
-// Scratch slots of the image layer.  A slot that grows is freed, so a pointer into it taken before is stale: a host form
-// and every _dev form it calls carve from disjoint slots, each with ONE rows::carve.
+// Scratch slots of the image layer, its lines of the library's table (pmi_common.h, where the rule stands):
 //   SCR_STAGE_A   host forms (Staged): pmi_render_hist / _gaussian, pmi_rotate_locs, pmi_render_hist_rot / _gaussian_rot,
-//                 pmi_blur, pmi_render_blurred; pmi_radial_sum's image; pmi_frc_curve_dev's two float64 images
-//   SCR_STAGE_B   rocPRIM temporaries (rows::two_pass) — so no arena of this layer; pmi_frc_curve_dev's spectra (it sorts
-//                 and scans nothing)
-//   SCR_STAGE_C   gaussian(): records, tile counts, offsets, tile bounds; pmi_frc_curve and pmi_radial_sum (host forms
-//                 that call no _dev form of this file)
+//                 pmi_blur, pmi_render_blurred
+//   SCR_STAGE_B   rocPRIM temporaries (rows::two_pass) — so no arena of this layer
+//   SCR_STAGE_C   gaussian(): records, tile counts, offsets, tile bounds
 //   SCR_STAGE_D   pmi_blur_dev: the image between the two passes
 //   SCR_RECORDS   tile_lists: the (tile, localization) pairs, unsorted and sorted
 // The histogram _dev forms and pmi_rotate_locs_dev take no scratch.
@@ -129,35 +126,6 @@ static int make_view(double oversampling, double y_min, double x_min, double y_m
     v->tiles_x = (int)((nx + TILE - 1) / TILE); v->tiles_y = (int)((ny + TILE - 1) / TILE);
     return PMI_OK;
 }
-
-// What a host form keeps on the device, in SCR_STAGE_A: every piece is named once, with the host array it is filled from
-// (`up`) or copied back to (`down`); place() carves them all and uploads, fetch() downloads.
-struct Staged {
-    struct Piece { void **dev; size_t bytes; const void *up; void *down; };
-    Piece pieces[12];
-    int n = 0;
-    template <typename T>
-    void add(T *&dev, size_t count, const void *up = nullptr, void *down = nullptr)
-    {
-        pieces[n++] = Piece{(void **)&dev, count * sizeof(T), up, down};
-    }
-    int place()
-    {
-        const int rc = rows::carve(SCR_STAGE_A, [&](rows::Arena &a) {
-            for (int k = 0; k < n; k++) *pieces[k].dev = a.take<char>(pieces[k].bytes);
-        });
-        if (rc != PMI_OK) return rc;
-        for (int k = 0; k < n; k++)
-            if (pieces[k].up && pieces[k].bytes) PMI_HIP(hipMemcpy(*pieces[k].dev, pieces[k].up, pieces[k].bytes, hipMemcpyHostToDevice));
-        return PMI_OK;
-    }
-    int fetch()
-    {
-        for (int k = 0; k < n; k++)
-            if (pieces[k].down && pieces[k].bytes) PMI_HIP(hipMemcpy(pieces[k].down, *pieces[k].dev, pieces[k].bytes, hipMemcpyDeviceToHost));
-        return PMI_OK;
-    }
-};
 
 // Behind a prep kernel that left locs[N] and ntiles[N] (offset: N entries; start: 2 * ntile entries, the second half
 // receives each tile's end): the tile lists.  Synchronises the stream once, the number of pairs *E sizes the sort buffers; with *E == 0 nothing is

@@ -322,7 +322,7 @@ int pmi_render_gaussian_rot_dev(const void *d_x, const void *d_y, const void *d_
 
 // Host forms: columns and results are staged in the library's scratch (render_common.h), the results copied back.
 // The coordinate columns of a rotated host form, of 4 or 8 bytes per value, named to `st`.
-static int rot_stage(pmi::rend::Staged &st, const void *x, const void *y, const void *z, int coords_f64, int64_t N, char *(&d)[3])
+static int rot_stage(pmi::Staged &st, const void *x, const void *y, const void *z, int coords_f64, int64_t N, char *(&d)[3])
 {
     using namespace pmi;
     if (pmi_device_count() < 1) { set_error("no HIP device"); return PMI_ERR_NODEVICE; }
@@ -337,7 +337,7 @@ int pmi_rotate_locs(const void *x, const void *y, const void *z, int coords_f64,
                     double *zr, uint8_t *in_view)
 {
     using namespace pmi;
-    rend::Staged st;
+    Staged st(SCR_STAGE_A);
     char *d[3] = {nullptr, nullptr, nullptr};
     int rc = rot_stage(st, x, y, z, coords_f64, N, d);
     if (rc != PMI_OK) return rc;
@@ -360,7 +360,7 @@ static int render_rot_host(const void *x, const void *y, const void *z, int coor
     if (!image || !n_rendered || (gaussian && N > 0 && (!lpx || !lpy))) { set_error("null pointer"); return PMI_ERR_ARG; }
     int rc = rend::check_image("render", ny, nx);
     if (rc != PMI_OK) return rc;
-    rend::Staged st;
+    Staged st(SCR_STAGE_A);
     char *d[3] = {nullptr, nullptr, nullptr};
     if ((rc = rot_stage(st, x, y, z, coords_f64, N, d)) != PMI_OK) return rc;
     float *dlx = nullptr, *dly = nullptr, *dlz = nullptr, *d_img = nullptr;

@@ -1,10 +1,10 @@
 // rows_common.h — what the kernels over a resident localization table share: launch shape, bisection, union-find, the
-// scratch arena, the rocPRIM sorts and scan (and the two passes of any rocPRIM call), the argument checks of a row table
+// rocPRIM sorts and scan (and the two passes of any rocPRIM call), the argument checks of a row table
 // and the dispatch over the x / y element types.  Included by aim, link, cluster, knn, frc and fiducials directly; centers, kinetics, combine, areas and average through rows_groups.h, the
 // layer for tables ordered by a label column; pairs, picks and similar through rows_blocks.h, the layer for tables in
-// block order; render, render_rot and blur through render_common.h, the layer of the image kernels, which takes the arena,
-// the sort and the scan from here and keeps the table of its scratch slots.  It pulls in rocPRIM: the fit kernels do not
-// pay for it.
+// block order; render, render_rot and blur through render_common.h, the layer of the image kernels, which takes the
+// sort and the scan from here.  It pulls in rocPRIM: the fit kernels do not pay for it, so the scratch arena and the
+// staging of the host forms, which they use too, live in pmi_common.h.
 #pragma once
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -73,35 +73,9 @@ static __global__ void iota_kernel(int32_t *a, int32_t *b /* may be null */, int
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------
-// one scratch slot cut into 256-byte aligned pieces; without a base it only measures
-struct Arena {
-    char *base = nullptr;
-    size_t used = 0;
-    template <typename T>
-    T *take(size_t count)
-    {
-        T *p = base ? (T *)(base + used) : nullptr;
-        used += (count * sizeof(T) + 255) & ~size_t(255);
-        return p;
-    }
-};
-
-// layout(Arena &) takes every piece of a call, in one order: it runs once to measure and once on the slot's buffer,
-// so the size asked for is the size used.  The pieces start at the first one taken and span *used bytes.
-template <typename Layout>
-static int carve(int slot, Layout &&layout, size_t *used = nullptr)
-{
-    Arena measure;
-    layout(measure);
-    void *base = nullptr;
-    const int rc = scratch(slot, measure.used, &base);
-    if (rc != PMI_OK) return rc;
-    Arena place;
-    place.base = (char *)base;
-    layout(place);
-    if (used) *used = place.used;
-    return PMI_OK;
-}
+// the scratch arena of pmi_common.h, under the names the row layers use
+using pmi::Arena;
+using pmi::carve;
 
 // the bits a radix sort needs for keys 0 .. top: at least one
 static int bits_of(uint64_t top)

@@ -201,21 +201,18 @@ int pmi_xcorr(const double *image_a, const double *image_b, int64_t Y, int64_t X
     int rc = xc::get_plans(Y, X, &pl);
     if (rc != PMI_OK) return rc;
     const int64_t npix = Y * X, nspec = Y * (X / 2 + 1);
-    void *d_img = nullptr, *d_spec = nullptr;
-    if ((rc = scratch(SCR_STAGE_A, (size_t)npix * 8 * 2, &d_img)) != PMI_OK) return rc;
-    if ((rc = scratch(SCR_STAGE_B, (size_t)nspec * 16 * 3, &d_spec)) != PMI_OK) return rc;
-    double *da = (double *)d_img, *db = da + npix;
-    hipfftDoubleComplex *fa = (hipfftDoubleComplex *)d_spec, *fb = fa + nspec, *fp = fb + nspec;
-    PMI_HIP(hipMemcpy(da, image_a, (size_t)npix * 8, hipMemcpyHostToDevice));
-    PMI_HIP(hipMemcpy(db, image_b, (size_t)npix * 8, hipMemcpyHostToDevice));
+    double *da = nullptr, *db = nullptr;
+    hipfftDoubleComplex *fa = nullptr, *fb = nullptr, *fp = nullptr;
+    Staged st(SCR_STAGE_A);
+    st.add(da, npix, image_a), st.add(db, npix, image_b, out), st.add(fa, nspec), st.add(fb, nspec), st.add(fp, nspec);
+    if ((rc = st.place()) != PMI_OK) return rc;
     if (hipfftExecD2Z(pl.fwd, da, fa) != HIPFFT_SUCCESS || hipfftExecD2Z(pl.fwd, db, fb) != HIPFFT_SUCCESS) { set_error("hipfftExecD2Z failed"); return PMI_ERR_HIP; }
     hipLaunchKernelGGL(xc::product_kernel, dim3((unsigned)((nspec + 255) / 256)), dim3(256), 0, 0, fa, fb, nspec, fp);
     if (hipfftExecZ2D(pl.inv, fp, da) != HIPFFT_SUCCESS) { set_error("hipfftExecZ2D failed"); return PMI_ERR_HIP; }
     hipLaunchKernelGGL(xc::shift_scale_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, 0, da, Y, X,
                        1.0 / (double)npix, 1.0 / std::sqrt((double)npix), db);
     PMI_HIP(hipGetLastError());
-    PMI_HIP(hipMemcpy(out, db, (size_t)npix * 8, hipMemcpyDeviceToHost));
-    return PMI_OK;
+    return st.fetch();
 }
 
 // *d_rois_out (optional): where the fit windows stay resident on the device until the next call that uses the
@@ -244,20 +241,15 @@ static int rcc_pair_list_impl(const double *segments, int64_t n_seg, int64_t Y, 
     crop_yx[0] = (int32_t)Y_; crop_yx[1] = (int32_t)X_;
     if (n_pairs == 0) return PMI_OK;
     const int64_t npix = Y * X, nspec = Y * (X / 2 + 1);
-    void *d_img = nullptr, *d_spec = nullptr, *d_work = nullptr, *d_out = nullptr;
-    if ((rc = scratch(SCR_STAGE_A, (size_t)n_seg * npix * 8, &d_img)) != PMI_OK) return rc;
-    if ((rc = scratch(SCR_STAGE_B, (size_t)n_seg * nspec * 16, &d_spec)) != PMI_OK) return rc;
-    if ((rc = scratch(SCR_STAGE_C, (size_t)nspec * 16 + (size_t)npix * 8 + 64, &d_work)) != PMI_OK) return rc;
-    if ((rc = scratch(SCR_STAGE_D, (size_t)n_pairs * (sizeof(xc::PeakOut) + (size_t)box * box * 8) + (size_t)n_seg * 8 + 64, &d_out)) != PMI_OK) return rc;
-    double *dseg = (double *)d_img;
-    hipfftDoubleComplex *spec = (hipfftDoubleComplex *)d_spec, *prod = (hipfftDoubleComplex *)d_work;
-    double *corr = (double *)(prod + nspec);
-    double *d_rois = (double *)d_out;
+    double *dseg = nullptr, *corr = nullptr, *d_rois = nullptr, *d_sums = nullptr;
+    hipfftDoubleComplex *spec = nullptr, *prod = nullptr;
+    xc::PeakOut *d_peaks = nullptr;
+    Staged st(SCR_STAGE_A);          // rcc_fit_peaks, which reads the windows left here, carves from SCR_FIT
+    st.add(dseg, (size_t)n_seg * npix, segments), st.add(spec, (size_t)n_seg * nspec), st.add(prod, nspec), st.add(corr, npix);
+    st.add(d_rois, (size_t)n_pairs * box * box, nullptr, fit_rois), st.add(d_sums, n_seg), st.add(d_peaks, n_pairs);
+    if ((rc = st.place()) != PMI_OK) return rc;
     if (d_rois_out) *d_rois_out = d_rois;
-    double *d_sums = d_rois + n_pairs * box * box;
-    xc::PeakOut *d_peaks = (xc::PeakOut *)(d_sums + n_seg);
-    PMI_HIP(hipMemcpy(dseg, segments, (size_t)n_seg * npix * 8, hipMemcpyHostToDevice));
-    PMI_HIP(hipMemsetAsync(d_sums, 0, (size_t)n_seg * 8, 0));
+    PMI_HIP(hipMemsetAsync(d_sums, 0, (size_t)n_seg * sizeof(double), 0));
     hipLaunchKernelGGL(xc::sum_kernel, dim3((unsigned)std::min<int64_t>(64, (npix + 255) / 256), (unsigned)n_seg), dim3(256), 0, 0,
                        dseg, npix, d_sums);
     std::vector<char> used((size_t)n_seg, 0);
@@ -265,7 +257,7 @@ static int rcc_pair_list_impl(const double *segments, int64_t n_seg, int64_t Y, 
     for (int64_t i = 0; i < n_seg; i++)
         if (used[(size_t)i] && hipfftExecD2Z(pl.fwd, dseg + i * npix, spec + i * nspec) != HIPFFT_SUCCESS) { set_error("hipfftExecD2Z failed"); return PMI_ERR_HIP; }
     std::vector<double> sums((size_t)n_seg);
-    PMI_HIP(hipMemcpy(sums.data(), d_sums, (size_t)n_seg * 8, hipMemcpyDeviceToHost));
+    PMI_HIP(hipMemcpy(sums.data(), d_sums, (size_t)n_seg * sizeof(double), hipMemcpyDeviceToHost));
     const double inv_n = 1.0 / (double)npix, inv_sqrt = 1.0 / std::sqrt((double)npix);
     std::vector<int64_t> skipped;
     for (int64_t pidx = 0; pidx < n_pairs; pidx++) {
@@ -280,7 +272,7 @@ static int rcc_pair_list_impl(const double *segments, int64_t n_seg, int64_t Y, 
     PMI_HIP(hipGetLastError());
     std::vector<xc::PeakOut> peaks((size_t)n_pairs);
     PMI_HIP(hipMemcpy(peaks.data(), d_peaks, (size_t)n_pairs * sizeof(xc::PeakOut), hipMemcpyDeviceToHost));
-    PMI_HIP(hipMemcpy(fit_rois, d_rois, (size_t)n_pairs * box * box * 8, hipMemcpyDeviceToHost));
+    if ((rc = st.fetch()) != PMI_OK) return rc;
     for (int64_t p = 0; p < n_pairs; p++) {
         peak_yx[2 * p] = peaks[(size_t)p].y_max; peak_yx[2 * p + 1] = peaks[(size_t)p].x_max;
         valid[p] = peaks[(size_t)p].valid;

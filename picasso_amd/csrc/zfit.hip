@@ -149,18 +149,14 @@ int pmi_zfit(const float *sx, const float *sy, int64_t N, const double *cx7, con
     if (pmi_device_count() < 1) { set_error("no HIP device"); return PMI_ERR_NODEVICE; }
     if (N == 0) return PMI_OK;
     if (!sx || !sy || !z || !sq) { set_error("null pointer"); return PMI_ERR_ARG; }
-    void *d_in = nullptr, *d_out = nullptr;
+    float *d_sx = nullptr, *d_sy = nullptr;
+    double *d_z = nullptr, *d_sq = nullptr;
+    Staged st(SCR_STAGE_A);
+    st.add(d_sx, N, sx), st.add(d_sy, N, sy), st.add(d_z, N, nullptr, z), st.add(d_sq, N, nullptr, sq);
     int rc;
-    if ((rc = scratch(SCR_STAGE_A, (size_t)N * 8, &d_in)) != PMI_OK) return rc;
-    if ((rc = scratch(SCR_STAGE_B, (size_t)N * 16, &d_out)) != PMI_OK) return rc;
-    float *d_sx = (float *)d_in, *d_sy = d_sx + N;
-    double *d_z = (double *)d_out, *d_sq = d_z + N;
-    PMI_HIP(hipMemcpy(d_sx, sx, (size_t)N * 4, hipMemcpyHostToDevice));
-    PMI_HIP(hipMemcpy(d_sy, sy, (size_t)N * 4, hipMemcpyHostToDevice));
+    if ((rc = st.place()) != PMI_OK) return rc;
     if ((rc = pmi_zfit_dev(d_sx, d_sy, N, nullptr, cx7, cy7, d_z, d_sq, nullptr)) != PMI_OK) return rc;
-    PMI_HIP(hipMemcpy(z, d_z, (size_t)N * 8, hipMemcpyDeviceToHost));
-    PMI_HIP(hipMemcpy(sq, d_sq, (size_t)N * 8, hipMemcpyDeviceToHost));
-    return PMI_OK;
+    return st.fetch();
 }
 
 int pmi_avgroi_dev(const float *d_spots, int64_t N, const int64_t *d_n, int box, float *d_theta, void *stream)
@@ -180,15 +176,13 @@ int pmi_avgroi(const float *spots, int64_t N, int box, float *theta)
     if (pmi_device_count() < 1) { set_error("no HIP device"); return PMI_ERR_NODEVICE; }
     if (N == 0) return PMI_OK;
     if (!spots || !theta) { set_error("null pointer"); return PMI_ERR_ARG; }
-    void *d_in = nullptr, *d_out = nullptr;
+    float *d_spots = nullptr, *d_theta = nullptr;
+    Staged st(SCR_STAGE_A);
+    st.add(d_spots, (size_t)N * box * box, spots), st.add(d_theta, (size_t)N * 6, nullptr, theta);
     int rc;
-    const size_t in_bytes = (size_t)N * box * box * 4;
-    if ((rc = scratch(SCR_STAGE_A, in_bytes, &d_in)) != PMI_OK) return rc;
-    if ((rc = scratch(SCR_STAGE_B, (size_t)N * 24, &d_out)) != PMI_OK) return rc;
-    PMI_HIP(hipMemcpy(d_in, spots, in_bytes, hipMemcpyHostToDevice));
-    if ((rc = pmi_avgroi_dev((const float *)d_in, N, nullptr, box, (float *)d_out, nullptr)) != PMI_OK) return rc;
-    PMI_HIP(hipMemcpy(theta, d_out, (size_t)N * 24, hipMemcpyDeviceToHost));
-    return PMI_OK;
+    if ((rc = st.place()) != PMI_OK) return rc;
+    if ((rc = pmi_avgroi_dev(d_spots, N, nullptr, box, d_theta, nullptr)) != PMI_OK) return rc;
+    return st.fetch();
 }
 
 }  // extern "C"
