@@ -64,6 +64,10 @@
  *                      picasso/render.py:739-773 render_hist_numba, the rotation and shift search, the transform)
  *   pmi_cumexp_fit*    picasso/lib.py:1263-1327 cumulative_exponential, fit_cum_exp, estimate_kinetic_rate, under
  *                      picasso/postprocess.py:1634-1917 evaluate_picks, pick_kinetics, pick_properties
+ *   pmi_g5m_*          picasso/g5m.py:212-318 _euclidean_distances, _kmeans_plusplus, :630-692 _check_G5M_resolution_2D,
+ *                      :695-817 _initialize_G5M_2D .. _m_step_2D, :820-902 _find_optimal_G5M_2D, :455-462, :1037-1043
+ *                      bic, n_parameters, :1699-1740 _estimate_gaussian_parameters_diag_cov, :1829-2064
+ *                      _convert_G5M_results, :2126-2298 _fit_G5M (picasso/lib.py:1243-1260 find_local_minima)
  *   pmi_kinetics_*     picasso/postprocess.py:1985-2004 _dark_times (:1920-1982 compute_dark_times,
  *                      dark_times), :3580-3649 groupprops
  *   pmi_pairs_*        picasso/postprocess.py:37-94 get_index_blocks, :169-204
@@ -1099,6 +1103,74 @@ int pmi_similar_shift_dev(const void *d_x, int x_type, const void *d_y, int y_ty
                           int32_t *d_out_n, double *d_out_rmsd, void *stream);
 int pmi_similar_filter(const double *cand_x, const double *cand_y, int64_t n_candidates, const double *pick_x,
                        const double *pick_y, int64_t n_picks, double d2, double cell, uint8_t *keep);
+
+/* ---- G5M molecular mapping in 2-D (picasso/g5m.py:820-902 _find_optimal_G5M_2D, :482-567 G5M.fit, :2126-2298
+ * _fit_G5M, :1829-2064 _convert_G5M_results; csrc/g5m.hip, csrc/g5m_core.h) ------------------------------------------ *
+ * Clusters are a CSR over float64 x, y, lp (lp: the mean of lpx and lpy per row; read only with "local" bounds but
+ * always present): int64 offsets[n_clusters + 1] ascending from 0 (checked).  The kernels draw no random numbers.  The
+ * caller draws, with NumPy's legacy generator, for every seed 42 + ii and every cluster size n: RandomState(seed), one
+ * choice(n) -> `first`, then uniform()s in order -> `uniform`; every K reads a prefix of them with its own
+ * n_local_trials = 2 + int(log K), (K - 1) n_local_trials values.  `table` holds 4 int64 per cluster: where its model
+ * starts in the model arrays (K_max = min(100, n / min_locs) components from there, or K for a fixed fit), where its
+ * first draws start in `first` (one per seed), where its uniforms start in `uniform`, and how many uniforms each seed has.
+ *
+ * flags: PMI_G5M_LP_ABS the sigma bounds are absolute (loc_prec_handle "abs"), else factors of the resp-weighted lp;
+ *        PMI_G5M_FORCE_SCRATCH the responsibilities live in the scratch arena even where n K <= PMI_G5M_LDS_RESP would keep
+ *        them in LDS (the same bits either way).
+ * The model arrays hold `total` components: model = 5 x total float64 (weights_ after set_parameters, means_ x, means_ y,
+ * covariances_, precisions_cholesky_, one plane behind the other), imodel = 2 x total int32 (n_locs of the valid
+ * components in valid order, then valid_idx padded with -1).  info = 4 int32 per cluster: the chosen K (0: no model), the
+ * number of valid components, converged, the last K tried.  bic: the model's BIC (inf without one, or for a fixed fit that
+ * the Sparrow criterion rejects).
+ *
+ * pmi_g5m_fit*        the search of _find_optimal_G5M_2D for every cluster: round r fits K = r with max(K, 3)
+ *                     initialisations for every cluster still searching, until K_max or max_rounds rounds without a better
+ *                     BIC.  `progress` (may be NULL) is called after every round with the round, the clusters it fitted
+ *                     and its device time in milliseconds.
+ * pmi_g5m_fit_fixed*  G5M_2D(n_components).fit for every cluster (a cluster of fewer rows than components gets no model),
+ *                     with optional means_init (n_clusters x n_components x 2 float64).
+ * pmi_g5m_assign*     _convert_G5M_results per cluster from its model (table: 2 int64 per cluster, the model's start and
+ *                     the start of its n x n_valid block in lp_out / wlp_out): per row the label and the log likelihood,
+ *                     per valid component stats = 7 float64 (frame, std_frame, mol_log_likelihood, p_val, the resp-weighted
+ *                     lp, the sum of its responsibilities, the resp-weighted log likelihood), n_events and the resp-weighted mean of every column of `cols`
+ *                     (n_cols x n_rows float64 -> col_means n_cols x total), per cluster group_log_likelihood.  frame is
+ *                     float64.  PMI_G5M_QUAD_F32: x and y hold float32 values and the quadratic form is accumulated in
+ *                     float32, as the reference does with a float32 table; PMI_G5M_FRAME_U32: frame differences wrap as
+ *                     uint32.  lp_out / wlp_out (may be NULL): estimate_log_prob and estimate_weighted_log_prob of the rows.
+ * The _dev forms take device arrays, run on `stream` and synchronise it; the others stage host arrays. */
+#define PMI_G5M_LDS_RESP 4096
+#define PMI_G5M_MAX_K 100
+#define PMI_G5M_LP_ABS 1
+#define PMI_G5M_FORCE_SCRATCH 2
+#define PMI_G5M_QUAD_F32 4
+#define PMI_G5M_FRAME_U32 8
+typedef void (*pmi_g5m_progress)(int round, int64_t clusters, double device_ms, void *user);
+int pmi_g5m_limits(int *lds_resp, int *max_k, int *threads);
+int pmi_g5m_fit_dev(const double *d_x, const double *d_y, const double *d_lp, const int64_t *d_offsets, int64_t n_clusters,
+                    int64_t n_rows, const int64_t *d_table, const int32_t *d_first, const double *d_uniform, int min_locs,
+                    double sigma_lo, double sigma_hi, int max_rounds, int flags, double *d_model, int32_t *d_imodel, int64_t total,
+                    int32_t *d_info, double *d_bic, pmi_g5m_progress progress, void *user, void *stream);
+int pmi_g5m_fit(const double *x, const double *y, const double *lp, const int64_t *offsets, int64_t n_clusters, const int64_t *table,
+                const int32_t *first, int64_t n_first, const double *uniform, int64_t n_uniform, int min_locs, double sigma_lo,
+                double sigma_hi, int max_rounds, int flags, double *model, int32_t *imodel, int64_t total, int32_t *info, double *bic,
+                pmi_g5m_progress progress, void *user);
+int pmi_g5m_fit_fixed_dev(const double *d_x, const double *d_y, const double *d_lp, const int64_t *d_offsets, int64_t n_clusters,
+                          int64_t n_rows, const int64_t *d_table, const int32_t *d_first, const double *d_uniform,
+                          const double *d_means_init, int n_components, int min_locs, double sigma_lo, double sigma_hi, int flags,
+                          double *d_model, int32_t *d_imodel, int64_t total, int32_t *d_info, double *d_bic, void *stream);
+int pmi_g5m_fit_fixed(const double *x, const double *y, const double *lp, const int64_t *offsets, int64_t n_clusters,
+                      const int64_t *table, const int32_t *first, int64_t n_first, const double *uniform, int64_t n_uniform,
+                      const double *means_init, int n_components, int min_locs, double sigma_lo, double sigma_hi, int flags,
+                      double *model, int32_t *imodel, int64_t total, int32_t *info, double *bic);
+int pmi_g5m_assign_dev(const double *d_x, const double *d_y, const double *d_lp, const double *d_frame, const int64_t *d_offsets,
+                       int64_t n_clusters, int64_t n_rows, const int64_t *d_table, const double *d_model, const int32_t *d_imodel,
+                       int64_t total, const int32_t *d_info, const double *d_cols, int n_cols, int flags, int32_t *d_label,
+                       double *d_loglik, double *d_stats, int32_t *d_events, double *d_group_ll, double *d_col_means, double *d_lp_out,
+                       double *d_wlp_out, int64_t n_prob, void *stream);
+int pmi_g5m_assign(const double *x, const double *y, const double *lp, const double *frame, const int64_t *offsets, int64_t n_clusters,
+                   const int64_t *table, const double *model, const int32_t *imodel, int64_t total, const int32_t *info,
+                   const double *cols, int n_cols, int flags, int32_t *label, double *loglik, double *stats, int32_t *events,
+                   double *group_ll, double *col_means, double *lp_out, double *wlp_out, int64_t n_prob);
 
 /* ---- timing hooks for bench.py (HIP events on the given stream) ------- */
 int pmi_event_create(void **event);

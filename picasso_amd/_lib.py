@@ -105,6 +105,16 @@ SYMBOLS = {
     "pmi_render_blurred": (_i32, [_p, _p, _i64, _f64, _f64, _f64, _f64, _f64, _p, _i64, _p, _i64, _i32, _f64, _p, _i64, _i64, _p]),
     "pmi_cumexp_fit_dev": (_i32, [_p, _i64, _p, _i64, _i32, _p, _p, _p]),
     "pmi_cumexp_fit": (_i32, [_p, _i64, _p, _i64, _i32, _p, _p]),
+    "pmi_g5m_limits": (_i32, [_p, _p, _p]),
+    "pmi_g5m_fit_dev": (_i32, [_p, _p, _p, _p, _i64, _i64, _p, _p, _p, _i32, _f64, _f64, _i32, _i32, _p, _p, _i64, _p, _p, _p, _p, _p]),
+    "pmi_g5m_fit": (_i32, [_p, _p, _p, _p, _i64, _p, _p, _i64, _p, _i64, _i32, _f64, _f64, _i32, _i32, _p, _p, _i64, _p, _p, _p, _p]),
+    "pmi_g5m_fit_fixed_dev": (_i32, [_p, _p, _p, _p, _i64, _i64, _p, _p, _p, _p, _i32, _i32, _f64, _f64, _i32, _p, _p, _i64, _p, _p,
+                                     _p]),
+    "pmi_g5m_fit_fixed": (_i32, [_p, _p, _p, _p, _i64, _p, _p, _i64, _p, _i64, _p, _i32, _i32, _f64, _f64, _i32, _p, _p, _i64, _p,
+                                 _p]),
+    "pmi_g5m_assign_dev": (_i32, [_p, _p, _p, _p, _p, _i64, _i64, _p, _p, _p, _i64, _p, _p, _i32, _i32, _p, _p, _p, _p, _p, _p, _p,
+                                  _p, _i64, _p]),
+    "pmi_g5m_assign": (_i32, [_p, _p, _p, _p, _p, _i64, _p, _p, _p, _i64, _p, _p, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _i64]),
     "pmi_xcorr": (_i32, [_p, _p, _i64, _i64, _p]),
     "pmi_rcc_pairs": (_i32, [_p, _i64, _i64, _i64, _i64, _i32, _p, _p, _p, _p]),
     "pmi_rcc_pair_list": (_i32, [_p, _i64, _i64, _i64, _i64, _i32, _p, _i64, _p, _p, _p, _p]),

@@ -2289,3 +2289,204 @@ def kinetic_rates(values, offsets) -> KineticRates:
         with _lib.lock():
             _lib.call("pmi_cumexp_fit", _lib.ptr(as_f64), len(as_f64), _lib.ptr(offsets), S, kind, _lib.ptr(fit), _lib.ptr(info))
     return KineticRates(fit[0], fit[1], fit[2], fit[3], info[0], info[1])
+
+
+# ---- G5M molecular mapping in 2-D (csrc/g5m.hip, picasso/g5m.py) ---------------------------------------------------------------
+G5M_LDS_RESP = 4096                # PMI_G5M_LDS_RESP: the most responsibilities (n K) a workgroup of the fit holds in LDS
+G5M_MAX_K = 100                    # PMI_G5M_MAX_K: N_COMPONENTS_MAX of picasso/g5m.py
+G5M_LP_ABS, G5M_FORCE_SCRATCH, G5M_QUAD_F32, G5M_FRAME_U32 = 1, 2, 4, 8
+G5M_SEED = 42                      # G5M.random_state
+G5M_STATS = ("frame", "std_frame", "mol_ll", "p_val", "lp", "rsum", "log_likelihood")
+G5M_PROGRESS = ctypes.CFUNCTYPE(None, ctypes.c_int, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p)
+
+
+def g5m_limits():
+    """(G5M_LDS_RESP, G5M_MAX_K, lanes of a workgroup) as the loaded library has them; a library built with other limits
+    than this module's is refused."""
+    vals = [ctypes.c_int(0) for _ in range(3)]
+    _lib.call("pmi_g5m_limits", *(ctypes.byref(v) for v in vals))
+    limits = tuple(int(v.value) for v in vals)
+    if limits[:2] != (G5M_LDS_RESP, G5M_MAX_K):
+        raise _lib.HipBackendError(f"libpicasso_hip.so has the G5M limits {limits[:2]}, this package {(G5M_LDS_RESP, G5M_MAX_K)}")
+    return limits
+
+
+def g5m_local_trials(n_components: int) -> int:
+    """``n_local_trials`` of ``_kmeans_plusplus`` (picasso/g5m.py:264)."""
+    return 2 + int(np.log(n_components))
+
+
+def g5m_draws_needed(n_components: int) -> int:
+    """Uniforms one seed of ``_kmeans_plusplus`` draws for that many components."""
+    return (n_components - 1) * g5m_local_trials(n_components)
+
+
+def g5m_draws(n_samples: int, n_seeds: int, n_uniform: int):
+    """What ``_kmeans_plusplus`` draws for a cluster of ``n_samples`` rows under the seeds 42 .. 42 + n_seeds - 1, with
+    NumPy's legacy generator: per seed ``RandomState(seed)``, one ``choice(n_samples)`` (int32) and the next ``n_uniform``
+    ``uniform()`` values in order (float64).  The draws depend on the seed, ``n_samples`` and the position in the stream
+    only, so one table serves every K."""
+    first = np.zeros(n_seeds, np.int32)
+    uniform = np.zeros((n_seeds, n_uniform), np.float64)
+    for ii in range(n_seeds):
+        rs = np.random.RandomState(G5M_SEED + ii)
+        first[ii] = rs.choice(n_samples)
+        uniform[ii] = rs.uniform(size=n_uniform)
+    return first, uniform
+
+
+class G5MModels(NamedTuple):
+    """The models of a table of clusters, ``cap[c]`` components from ``start[c]`` on in every plane: ``model`` (5 x total
+    float64: weights_, means_ x, means_ y, covariances_, precisions_cholesky_), ``imodel`` (2 x total int32: n_locs of the
+    valid components in valid order, valid_idx padded with -1), ``info`` (n x 4 int32: K or 0, valid components,
+    converged, last K tried) and ``bic``."""
+    start: np.ndarray
+    cap: np.ndarray
+    model: np.ndarray
+    imodel: np.ndarray
+    info: np.ndarray
+    bic: np.ndarray
+
+    def of(self, c: int):
+        """(weights_, means_, covariances_, precisions_cholesky_, valid_idx, n_locs, converged) of cluster c, or None."""
+        K, nv = int(self.info[c, 0]), int(self.info[c, 1])
+        if K == 0:
+            return None
+        s = slice(int(self.start[c]), int(self.start[c]) + K)
+        return (self.model[0, s].copy(), np.stack([self.model[1, s], self.model[2, s]], axis=1), self.model[3, s].copy(),
+                self.model[4, s].copy(), self.imodel[1, s][:nv].copy(), self.imodel[0, s][:nv].copy(), bool(self.info[c, 2]))
+
+
+def _g5m_rows(x, y, lp, offsets):
+    x, y, lp = (np.ascontiguousarray(a, np.float64) for a in (x, y, lp))
+    offsets = np.ascontiguousarray(_index_column(offsets, "offsets"))
+    if offsets.ndim != 1 or len(offsets) < 1 or offsets[0] != 0 or (np.diff(offsets) < 0).any() or offsets[-1] != len(x):
+        raise ValueError("offsets must be the C + 1 ascending offsets of the clusters, from 0 to len(x)")
+    if not (x.ndim == 1 and x.shape == y.shape == lp.shape):
+        raise ValueError("x, y and lp must be columns of one length")
+    return x, y, lp, offsets
+
+
+def g5m_table(sizes, caps):
+    """The draws of a table of clusters of ``sizes`` rows that fit up to ``caps`` components each: (table, first, uniform)
+    as pmi_g5m_fit takes them, drawn once per distinct (size, cap)."""
+    sizes, caps = np.asarray(sizes, np.int64), np.asarray(caps, np.int64)
+    table = np.zeros((len(sizes), 4), np.int64)
+    table[:, 0] = np.cumsum(caps) - caps
+    firsts, uniforms, seen, n_first, n_uniform = [], [], {}, 0, 0
+    for c, (n, cap) in enumerate(zip(sizes.tolist(), caps.tolist())):
+        if cap < 1:
+            continue
+        if (n, cap) not in seen:
+            seeds, stride = max(cap, 3), g5m_draws_needed(cap)
+            f, u = g5m_draws(n, seeds, stride)
+            seen[n, cap] = (n_first, n_uniform, stride)
+            firsts.append(f), uniforms.append(u.ravel())
+            n_first, n_uniform = n_first + seeds, n_uniform + seeds * stride
+        table[c, 1:] = seen[n, cap]
+    first = np.concatenate(firsts + [np.zeros(1, np.int32)])
+    uniform = np.concatenate(uniforms + [np.zeros(1, np.float64)])
+    return table, first, uniform
+
+
+def _g5m_empty(caps):
+    total = int(caps.sum())
+    start = np.cumsum(caps) - caps
+    return G5MModels(start, caps, np.zeros((5, total), np.float64), np.zeros((2, total), np.int32),
+                     np.zeros((len(caps), 4), np.int32), np.full(len(caps), np.inf))
+
+
+def g5m_search(x, y, lp, offsets, *, min_locs, sigma_bounds, lp_abs=False, max_rounds=3, force_scratch=False,
+               progress=None) -> G5MModels:
+    """``_find_optimal_G5M_2D`` of every cluster ``[offsets[c], offsets[c + 1])`` of the float64 rows in one device call
+    (pmi_g5m_fit).  ``progress(round, clusters, device_ms)`` is called after every round."""
+    _lib.require_gpu()
+    x, y, lp, offsets = _g5m_rows(x, y, lp, offsets)
+    sizes = np.diff(offsets)
+    caps = np.minimum(G5M_MAX_K, sizes // int(min_locs))
+    out = _g5m_empty(caps)
+    if not len(sizes):
+        return out
+    table, first, uniform = g5m_table(sizes, caps)
+    cb = G5M_PROGRESS((lambda r, n, ms, _u: progress(int(r), int(n), float(ms))) if progress else 0)
+    flags = (G5M_LP_ABS if lp_abs else 0) | (G5M_FORCE_SCRATCH if force_scratch else 0)
+    with _lib.lock():
+        _lib.call("pmi_g5m_fit", _lib.ptr(x), _lib.ptr(y), _lib.ptr(lp), _lib.ptr(offsets), len(sizes), _lib.ptr(table), _lib.ptr(first),
+                  len(first), _lib.ptr(uniform), len(uniform), int(min_locs), float(sigma_bounds[0]), float(sigma_bounds[1]),
+                  int(max_rounds), flags, _lib.ptr(out.model), _lib.ptr(out.imodel), int(caps.sum()), _lib.ptr(out.info),
+                  _lib.ptr(out.bic), cb, None)
+    return out
+
+
+def g5m_fit_fixed(x, y, lp, offsets, n_components, *, min_locs, sigma_bounds, lp_abs=False, means_init=None,
+                  force_scratch=False) -> G5MModels:
+    """``G5M_2D(n_components, ...).fit`` of every cluster in one device call (pmi_g5m_fit_fixed); ``means_init`` is
+    (clusters, n_components, 2) or None."""
+    _lib.require_gpu()
+    x, y, lp, offsets = _g5m_rows(x, y, lp, offsets)
+    K = int(n_components)
+    if not 1 <= K <= G5M_MAX_K:
+        raise ValueError(f"n_components must be 1 .. {G5M_MAX_K}")
+    sizes = np.diff(offsets)
+    caps = np.where(sizes >= K, K, 0).astype(np.int64)
+    out = _g5m_empty(np.full(len(sizes), K, np.int64))
+    if not len(sizes):
+        return out
+    table, first, uniform = g5m_table(sizes, caps)
+    table[:, 0] = out.start
+    if means_init is not None:
+        means_init = np.ascontiguousarray(means_init, np.float64)
+        if means_init.shape != (len(sizes), K, 2):
+            raise ValueError(f"means_init must have the shape {(len(sizes), K, 2)}")
+    flags = (G5M_LP_ABS if lp_abs else 0) | (G5M_FORCE_SCRATCH if force_scratch else 0)
+    with _lib.lock():
+        _lib.call("pmi_g5m_fit_fixed", _lib.ptr(x), _lib.ptr(y), _lib.ptr(lp), _lib.ptr(offsets), len(sizes), _lib.ptr(table),
+                  _lib.ptr(first), len(first), _lib.ptr(uniform), len(uniform), _lib.ptr(means_init), K, int(min_locs),
+                  float(sigma_bounds[0]), float(sigma_bounds[1]), flags, _lib.ptr(out.model), _lib.ptr(out.imodel), len(sizes) * K,
+                  _lib.ptr(out.info), _lib.ptr(out.bic))
+    return out
+
+
+class G5MAssigned(NamedTuple):
+    """Per row ``label`` (int32) and ``log_likelihood``; per component slot of the models ``stats`` (total x 7: G5M_STATS),
+    ``n_events`` and ``col_means`` (columns x total); per cluster ``group_ll``; optionally per cluster the (n, n_valid) log
+    probabilities without and with the weights."""
+    label: np.ndarray
+    log_likelihood: np.ndarray
+    stats: np.ndarray
+    n_events: np.ndarray
+    group_ll: np.ndarray
+    col_means: np.ndarray
+    log_prob: list
+    weighted_log_prob: list
+
+
+def g5m_assign(x, y, lp, frame, offsets, models: G5MModels, cols=None, *, f32=True, frame_u32=False, probs=False) -> G5MAssigned:
+    """What ``_convert_G5M_results`` computes per cluster from its model, in one device call (pmi_g5m_assign).  ``f32``:
+    x and y came from a float32 table (the reference then accumulates the quadratic form in float32)."""
+    _lib.require_gpu()
+    x, y, lp, offsets = _g5m_rows(x, y, lp, offsets)
+    frame = np.ascontiguousarray(frame, np.float64)
+    n_rows, C, total = len(x), len(offsets) - 1, models.model.shape[1]
+    cols = np.zeros((0, n_rows), np.float64) if cols is None else np.ascontiguousarray(cols, np.float64).reshape(-1, n_rows)
+    sizes = np.diff(offsets)
+    blocks = sizes * models.info[:, 1]
+    table = np.ascontiguousarray(np.stack([models.start, np.cumsum(blocks) - blocks], axis=1), np.int64)
+    n_prob = int(blocks.sum()) if probs else 0
+    out = G5MAssigned(np.zeros(n_rows, np.int32), np.zeros(n_rows, np.float64), np.zeros((total, len(G5M_STATS)), np.float64), np.zeros(total, np.int32),
+                      np.zeros(C, np.float64), np.zeros((len(cols), total), np.float64), [], [])
+    lp_out = np.zeros(max(n_prob, 1), np.float64) if probs else None
+    wlp_out = np.zeros(max(n_prob, 1), np.float64) if probs else None
+    flags = (G5M_QUAD_F32 if f32 else 0) | (G5M_FRAME_U32 if frame_u32 else 0)
+    if C:
+        with _lib.lock():
+            _lib.call("pmi_g5m_assign", _lib.ptr(x), _lib.ptr(y), _lib.ptr(lp), _lib.ptr(frame), _lib.ptr(offsets), C, _lib.ptr(table),
+                      _lib.ptr(np.ascontiguousarray(models.model)), _lib.ptr(np.ascontiguousarray(models.imodel)), total,
+                      _lib.ptr(np.ascontiguousarray(models.info)), _lib.ptr(cols) if len(cols) else None, len(cols), flags,
+                      _lib.ptr(out.label), _lib.ptr(out.log_likelihood), _lib.ptr(out.stats), _lib.ptr(out.n_events),
+                      _lib.ptr(out.group_ll), _lib.ptr(out.col_means) if len(cols) else None, _lib.ptr(lp_out), _lib.ptr(wlp_out), n_prob)
+    if probs:
+        for c in range(C):
+            s, shape = slice(int(table[c, 1]), int(table[c, 1] + blocks[c])), (int(sizes[c]), int(models.info[c, 1]))
+            out.log_prob.append(lp_out[s].reshape(shape)), out.weighted_log_prob.append(wlp_out[s].reshape(shape))
+    return out

@@ -55,15 +55,17 @@ int device_cu_count();                // compute units of that device (cached pe
 //                       pmi_knn_order_dev, pmi_pairs_order_dev / _density_dev / _distance_hist_dev, pmi_picks_circle_dev /
 //                       _shape_dev, pmi_similar_shift_dev, pmi_centers_order_dev / _stats_dev / _hull_dev,
 //                       pmi_kinetics_dark_order_dev / _stats_dev, pmi_combine_order_dev / _stats_dev / _mindist_dev,
-//                       pmi_fiducials_drift_dev, pmi_cumexp_fit_dev, pmi_frc_curve_dev
+//                       pmi_fiducials_drift_dev, pmi_cumexp_fit_dev, pmi_frc_curve_dev, pmi_g5m_fit_dev / _fit_fixed_dev
+//                       (the search state and one round's records), pmi_g5m_assign_dev
 //   SCR_STAGE_B   host  none
 //                 _dev  every rocPRIM temporary (rows::two_pass: the sorts and scans of the row, group, block and image
-//                       layers, pmi_cumexp_fit_dev's segmented sort) and pmi_frc_curve_dev's spectra (it sorts nothing)
-//   SCR_STAGE_C   host  pmi_cumexp_fit, pmi_frc_curve, pmi_aim_roi_cc
+//                       layers, pmi_cumexp_fit_dev's segmented sort) and pmi_frc_curve_dev's spectra (it sorts nothing),
+//                       pmi_g5m_fit_dev / _fit_fixed_dev's responsibilities beyond LDS (they sort nothing)
+//   SCR_STAGE_C   host  pmi_cumexp_fit, pmi_frc_curve, pmi_aim_roi_cc, pmi_g5m_fit, pmi_g5m_fit_fixed, pmi_g5m_assign (inputs)
 //                 _dev  the cut spots of a fit from the movie (fit_impl: pmi_gaussmle_movie_dev, pmi_localize_mle_dev;
 //                       lq::launch: pmi_gausslq_movie_dev, pmi_localize_lq_dev), pmi_cluster_smlm_dev and
 //                       pmi_cluster_frame_analysis_dev, the Gaussian renders (render_common.h)
-//   SCR_STAGE_D   host  pmi_peak_fit
+//   SCR_STAGE_D   host  pmi_peak_fit, pmi_g5m_assign (outputs)
 //                 _dev  the work arrays of every MLE and least-squares fit (fit_impl, lq::launch), pmi_blur_dev
 //   SCR_FIT       host  pmi_rcc_shifts (rcc_fit_peaks, behind rcc_pair_list_impl's SCR_STAGE_A)
 //                 _dev  every MLE fit (fit_impl)

@@ -353,7 +353,7 @@ void release_fft_plans();   // xcorr.hip
 
 extern "C" {
 
-int pmi_version(void) { return 125; }   // 0.1.25: + pmi_rotate_locs / pmi_render_hist_rot / pmi_render_gaussian_rot and their _dev forms (rotated views); 0.1.24: + pmi_cumexp_fit_dev / pmi_cumexp_fit (kinetic rates of picks); 0.1.23: + pmi_blur_dev / pmi_blur / pmi_render_blurred (image blur); 0.1.22: + pmi_similar_shift_dev / pmi_similar_filter (pick_similar); 0.1.21: + pmi_fiducials_* (fiducial undrift); 0.1.20: + pmi_picks_* (picked localizations); 0.1.19: + pmi_frc_* / pmi_radial_sum (Fourier ring correlation); 0.1.18: + pmi_average_* (particle averaging); 0.1.17: + pmi_localize_reset_defer_prior / pmi_localize_last_scan_decisions (accept-rate prior of the deferring scan); 0.1.16: + pmi_areas_* (cluster areas and volumes); 0.1.15: + pmi_combine_* (cluster combine and its nearest-cluster distances); 0.1.14: + pmi_knn_* (nearest-neighbour distances); 0.1.13: + pmi_kinetics_* (dark times, group properties); 0.1.12: + pmi_centers_* (cluster centers); 0.1.11: + pmi_pairs_* (local density, distance histogram); 0.1.10: + pmi_cluster_* (DBSCAN, the SMLM clusterer); 0.1.9: + pmi_link_* / pmi_nena_hist_dev (link, NeNA); 0.1.8: - the pixel hand-off from the scan to the fit and its setter; 0.1.7: + pmi_aim_* (AIM undrift); 0.1.6: round 6 (32-bit integer movies on the key scan, side lanes per (device, bank); + pmi_mle_set_libm / pmi_mle_get_libm / pmi_libm_eval_dev)
+int pmi_version(void) { return 126; }   // 0.1.26: + pmi_g5m_* (G5M molecular mapping in 2-D); 0.1.25: + pmi_rotate_locs / pmi_render_hist_rot / pmi_render_gaussian_rot and their _dev forms (rotated views); 0.1.24: + pmi_cumexp_fit_dev / pmi_cumexp_fit (kinetic rates of picks); 0.1.23: + pmi_blur_dev / pmi_blur / pmi_render_blurred (image blur); 0.1.22: + pmi_similar_shift_dev / pmi_similar_filter (pick_similar); 0.1.21: + pmi_fiducials_* (fiducial undrift); 0.1.20: + pmi_picks_* (picked localizations); 0.1.19: + pmi_frc_* / pmi_radial_sum (Fourier ring correlation); 0.1.18: + pmi_average_* (particle averaging); 0.1.17: + pmi_localize_reset_defer_prior / pmi_localize_last_scan_decisions (accept-rate prior of the deferring scan); 0.1.16: + pmi_areas_* (cluster areas and volumes); 0.1.15: + pmi_combine_* (cluster combine and its nearest-cluster distances); 0.1.14: + pmi_knn_* (nearest-neighbour distances); 0.1.13: + pmi_kinetics_* (dark times, group properties); 0.1.12: + pmi_centers_* (cluster centers); 0.1.11: + pmi_pairs_* (local density, distance histogram); 0.1.10: + pmi_cluster_* (DBSCAN, the SMLM clusterer); 0.1.9: + pmi_link_* / pmi_nena_hist_dev (link, NeNA); 0.1.8: - the pixel hand-off from the scan to the fit and its setter; 0.1.7: + pmi_aim_* (AIM undrift); 0.1.6: round 6 (32-bit integer movies on the key scan, side lanes per (device, bank); + pmi_mle_set_libm / pmi_mle_get_libm / pmi_libm_eval_dev)
 
 const char *pmi_last_error(void) { return pmi::g_err; }
 

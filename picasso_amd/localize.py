@@ -825,7 +825,8 @@ def _reference_module(given, name: str):
 
 def install(picasso_localize=None, picasso_gaussmle=None, picasso_gausslq=None, picasso_zfit=None,
             picasso_render=None, picasso_imageprocess=None, picasso_postprocess=None, *, fused: bool = False,
-            devices=None, picasso_aim=None, picasso_clusterer=None, picasso_spinna=None, picasso_average=None) -> None:
+            devices=None, picasso_aim=None, picasso_clusterer=None, picasso_spinna=None, picasso_g5m=None,
+            picasso_average=None) -> None:
     """Rebind the reference package's hot-path functions to this backend, so that
     picasso.__main__ and the GUI run on the GPU unchanged.  Modules not given are taken
     from the installed ``picasso`` package; the rows next to the path (z fit, render, RCC undrift) are rebound
@@ -851,7 +852,8 @@ def install(picasso_localize=None, picasso_gaussmle=None, picasso_gausslq=None, 
     (``postprocess.FRC_NAMES``: ``frc``, ``_frc``) with ``picasso.imageprocess.radial_sum`` under it, which Render's
     resolution box calls (``plot_frc`` stays the reference's own).
     ``picasso_average``, when given, gets the particle averaging (``average.AVERAGE_NAMES``: ``average`` and the helpers
-    beside it), which `picasso average` and the Average GUI call."""
+    beside it), which `picasso average` and the Average GUI call.  ``picasso_g5m``, when given, gets G5M molecular mapping
+    in 2-D (``g5m.G5M_NAMES``: ``g5m`` and ``G5M_2D``), which `picasso g5m` and Render call; the 3-D class stays its own."""
     if picasso_localize is None:
         import picasso.localize as picasso_localize       # the installed reference
     if picasso_gaussmle is None:
@@ -926,3 +928,7 @@ def install(picasso_localize=None, picasso_gaussmle=None, picasso_gausslq=None, 
         from . import average as amd_average
         for name in amd_average.AVERAGE_NAMES:
             setattr(picasso_average, name, getattr(amd_average, name))
+    if picasso_g5m is not None:
+        from . import g5m as amd_g5m
+        for name in amd_g5m.G5M_NAMES:
+            setattr(picasso_g5m, name, getattr(amd_g5m, name))
